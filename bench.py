@@ -13,6 +13,9 @@ One JSON line is printed by rank 0:
   roofline     : filtered_lrelu streaming kernel -- algorithmic bytes (C*(in^2+out^2)*4 per image and layer,
                  SURVEY 8d) / its summed launch time measured with HIP events on the launch stream, vs 8 TB/s
   cpu_baseline : the CPU oracle (C/OpenMP port of the reference ref path) timed on this host for ONE image
+
+--dump-outputs DIR writes the images of the last timed step (rank 0) to DIR as .npy files: inputs and weights are seeded, so
+two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -360,6 +363,25 @@ def bench_extras(G, ws, device, steps=5, timer=None):
     return out
 
 
+DUMP_SAMPLE = 1 << 22        # elements of the seeded sample of the whole batch (16 MB in float32)
+
+
+def dump_outputs(img, out_dir):
+    """--dump-outputs: what the timed path returned in its last step, for output-by-output comparison of two builds on the same
+    arguments.  The whole [B, 3, R, R] batch is 96 MB at the default workload, so three views of it are written (28 MB there):
+      image0.npy               the first image, complete (float32)
+      images_sample.npy        the batch at DUMP_SAMPLE flat positions drawn by a fixed seed (float32; the whole batch when smaller)
+      images_channel_mean.npy  the mean of every image's every channel over all pixels, [B, 3] (float64)"""
+    a = img.detach().float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    flat = a.reshape(-1)
+    if flat.size > DUMP_SAMPLE:
+        flat = flat[np.sort(np.random.RandomState(0).randint(0, flat.size, size=DUMP_SAMPLE))]
+    np.save(os.path.join(out_dir, 'image0.npy'), np.ascontiguousarray(a[0]))
+    np.save(os.path.join(out_dir, 'images_sample.npy'), np.ascontiguousarray(flat))
+    np.save(os.path.join(out_dir, 'images_channel_mean.npy'), a.astype(np.float64).mean(axis=(2, 3)))
+
+
 def launch_ranks(args, argv):
     """`python bench.py --gpus N` with N > 1 and no rendezvous in the environment: start the N ranks as FRESH child processes
     (torch.distributed.run, one rank per GPU, RCCL), relay rank 0's single JSON line and the children's exit status.  This
@@ -426,7 +448,11 @@ def main(argv=None):
     ap.add_argument('--eager', action='store_true', help='launch kernel by kernel instead of replaying a captured hipGraph')
     ap.add_argument('--no-extras', action='store_true', help='skip the secondary mixed-precision / config-R measurements')
     ap.add_argument('--dry-run', action='store_true', help='CPU rehearsal of the launch path (gloo, stub step); prints a line with value null')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="after the timed steps, write rank 0's images of the last timed step to DIR as .npy (see dump_outputs)")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # the driver's scaling run calls `python bench.py --gpus N` directly: this process becomes the launcher (before any GPU use)
@@ -496,6 +522,8 @@ def main(argv=None):
         dist.barrier()
     dt = time.perf_counter() - t0
     timer.enabled = False
+    if args.dump_outputs and rank == 0:
+        dump_outputs(img, args.dump_outputs)         # before anything else runs: the graph's output buffer is reused by a replay
     ksteps = args.steps
     if graphed is not None:
         # same kernels, same inputs, launched eagerly so each launch can be bracketed by events on its stream

@@ -46,3 +46,29 @@ def test_failing_rank_fails_the_launch():
         pytest.skip('needs a host without GPUs')
     r = _run(['--gpus', '2', '--steps', '1', '--warmup', '0'])
     assert r.returncode != 0 and r.stdout.strip() == ''
+
+
+def test_dump_outputs_is_seeded_bounded_and_float(tmp_path):
+    """--dump-outputs: the same images give the same files, in float32 / float64, within 64 MB for the default workload's shape."""
+    import numpy as np
+    import torch
+    import bench
+    img = torch.from_numpy(np.random.RandomState(5).randn(8, 3, 1024, 1024).astype(np.float32))
+    bench.dump_outputs(img, str(tmp_path / 'a'))
+    bench.dump_outputs(img.clone(), str(tmp_path / 'b'))
+    names = sorted(os.listdir(tmp_path / 'a'))
+    assert names == ['image0.npy', 'images_channel_mean.npy', 'images_sample.npy']
+    assert sum(os.path.getsize(tmp_path / 'a' / n) for n in names) <= 64 << 20
+    for n in names:
+        a, b = np.load(tmp_path / 'a' / n), np.load(tmp_path / 'b' / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+    assert np.array_equal(np.load(tmp_path / 'a' / 'image0.npy'), img[0].numpy())
+    assert np.allclose(np.load(tmp_path / 'a' / 'images_channel_mean.npy'), img.double().mean(dim=(2, 3)).numpy())
+    small = torch.arange(24, dtype=torch.float32).view(2, 3, 2, 2)          # below the sample size: the whole batch is written
+    bench.dump_outputs(small, str(tmp_path / 'c'))
+    assert np.array_equal(np.load(tmp_path / 'c' / 'images_sample.npy'), small.numpy().reshape(-1))
+
+
+def test_steps_below_one_is_an_error():
+    r = _run(['--dry-run', '--steps', '0'])
+    assert r.returncode != 0 and '--steps must be at least 1' in r.stderr
