@@ -576,6 +576,35 @@ SG3_API long long sg3_head_gemm_packed_halfs(int32_t G, int32_t K, int32_t N);
 SG3_API int sg3_head_gemm_pack(const float* w, void* packed, int32_t G, int32_t K, int32_t N, int32_t* rangeFlag, void* stream);
 SG3_API int sg3_head_gemm(const sg3_head_gemm_params* p, void* stream);
 
+/* ----------------------------------------------------------------------
+ * Image finishing of the editing scripts (reference utils/common.py:39-45 tensor2im, then PIL Image.resize((w, h)) with its
+ * default BICUBIC filter as inversion/scripts/inference_editing.py:82-85 uses it): for every image b of x [B,3,H,W] float32
+ *     y[b] = np.array(tensor2im(x[b]).resize((w, h)))        uint8 [h,w,3], bit-identical (NaN input is outside the contract)
+ * One launch for all B images.  Strides are in elements (x: n, c, y, x; y: n, y, x, c -- bytes), any layout, so y may be a
+ * column band of a wider strip.  A dimension whose size changes needs its table from sg3_resample_coeffs, copied to the device
+ * by the caller (boundsH / coeffsH for W -> w, boundsV / coeffsV for H -> h); unused tables may be NULL.  When neither changes,
+ * the images are converted without filtering, as PIL returns a copy.
+ * sg3_resample_coeffs (host only): PIL's fixed-point bicubic taps for in -> out samples: bounds [out][2] = (first input sample,
+ * tap count), coeffs [out][ksize] int32 (22 fractional bits, normalised in double precision); returns ksize, or the ksize alone
+ * when both arrays are NULL; < 0 on a bad size.
+ * ---------------------------------------------------------------------- */
+typedef struct sg3_image_finish_params {
+    const float*   x;              /* [B,3,H,W] */
+    int64_t        xStride[4];
+    uint8_t*       y;              /* [B,h,w,3] */
+    int64_t        yStride[4];
+    int32_t        B, H, W, h, w;
+    const int32_t* boundsH;        /* [w][2] */
+    const int32_t* coeffsH;        /* [w][kH] */
+    int32_t        kH;
+    const int32_t* boundsV;        /* [h][2] */
+    const int32_t* coeffsV;        /* [h][kV] */
+    int32_t        kV;
+} sg3_image_finish_params;
+
+SG3_API int sg3_resample_coeffs(int32_t inSize, int32_t outSize, int32_t* bounds, int32_t* coeffs);
+SG3_API int sg3_image_finish(const sg3_image_finish_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -112,6 +112,12 @@ class Conv2dParams(ctypes.Structure):
                 ('act', c_i32), ('precision', c_i32), ('rangeFlag', c_vp)]
 
 
+class ImageFinishParams(ctypes.Structure):
+    _fields_ = [('x', c_vp), ('xStride', c_i64 * 4), ('y', c_vp), ('yStride', c_i64 * 4),
+                ('B', c_i32), ('H', c_i32), ('W', c_i32), ('h', c_i32), ('w', c_i32),
+                ('boundsH', c_vp), ('coeffsH', c_vp), ('kH', c_i32), ('boundsV', c_vp), ('coeffsV', c_vp), ('kV', c_i32)]
+
+
 # every symbol include/sg3_ops.h declares: (name, restype, argtypes)
 EXPORTS = [
     ('sg3_abi_version', ctypes.c_int, []),
@@ -148,6 +154,8 @@ EXPORTS = [
     ('sg3_conv2d_wgrad_splits', ctypes.c_int, [ctypes.c_int] * 7 + [ctypes.POINTER(ctypes.c_int)] * 2),
     ('sg3_conv2d_wgrad', ctypes.c_int, [ctypes.POINTER(WgradParams), c_vp]),
     ('sg3_conv2d_pack', ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp]),
+    ('sg3_resample_coeffs', ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, c_vp, c_vp]),
+    ('sg3_image_finish', ctypes.c_int, [ctypes.POINTER(ImageFinishParams), c_vp]),
 ]
 
 _lib = None
