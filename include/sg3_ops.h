@@ -129,6 +129,11 @@ SG3_API int sg3_filtered_lrelu_finish_partials(const float* sumPartial, const fl
  * 0 when the call does not take the streaming kernel.  For tests and profiling; no reference counterpart. */
 SG3_API int sg3_filtered_lrelu_planes_per_wave(const sg3_filtered_lrelu_params* p);
 
+/* host-only: the bound on |input + bias| under which the plain forward's streaming kernel evaluates lrelu + clamp as one
+ * med3(u, slope*u, clamp/gain) -- the same computation the kernel makes from the separable up filter fu (fuW taps, HOST
+ * memory here).  -1 when there is none (clamp/gain not positive). */
+SG3_API float sg3_filtered_lrelu_fast_threshold(const float* fu, int fuW, int up, float gain, float slope, float clamp);
+
 /* 1 when sg3_filtered_lrelu has a fused kernel for this tuple (host-only
  * query; mirrors the reference's choose_filtered_lrelu_kernel test call,
  * torch_utils/ops/filtered_lrelu.cpp:46-56). */

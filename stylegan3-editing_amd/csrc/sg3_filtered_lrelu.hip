@@ -82,6 +82,7 @@ struct StreamParams {
     int totalBlocks;
     float gain, slope, clamp;
     int flip;
+    int fastAct;                   // plain forward: 1 = try the one-instruction activation first (see `fast_threshold`), 0 = never
     float* ysum;                   // optional [N*C][nChunks*nStrips]: sum of this block's outputs (adjoint passes only: their bias gradient)
     float* ymax;                   // optional, same shape: max |output| of this block (adjoint passes only: the operand bound of the
                                    // convolution gradients that read the result next)
@@ -268,6 +269,25 @@ struct WaveState {
     int ooff[2];                  // packed mode: byte offsets of this lane's two output columns from the first plane's row (out of range: none)
 };
 
+// Threshold of the one-instruction activation (plain forward).  The kernel forms every upsampled sample u from staged samples x
+// (input + bias) through one phase of the separable up filter per direction, taps scaled by `up`: |u| <= hv * max |x| with
+// hv = (up * max over phases of sum |f|)^2 (the phases map onto each other under flip).  For max |x| <= T, slope |u| <= clamp / gain
+// holds -- with a 1e-4 margin over the rounding of the sums, of T and of u -- and |u| stays far below overflow.  -1: no fast path.
+// Host and device run this same code (sg3_filtered_lrelu_fast_threshold exposes it to the CPU tests).
+__host__ __device__ static inline float fast_threshold(const float* fu, int taps, int up, float gain, float slope, float clamp) {
+    const float clampv = clamp / gain;                 // as the kernel forms it
+    if (!(clampv > 0.f)) return -1.f;
+    float hs = 0.f;
+    for (int ph = 0; ph < up; ph++) {
+        float s = 0.f;
+        for (int k = ph; k < taps; k += up) s += fabsf(fu[k]);
+        hs = fmaxf(hs, s);
+    }
+    hs *= (float)up;
+    const float hv = hs * hs;
+    return fminf(clampv / (slope * hv), 0x1p124f / fmaxf(hv, 1.f)) * 0.9999f;
+}
+
 // SIGNS: 0 = plain forward; 1 = forward that also writes the sign tensor (training); 2 = adjoint pass: the stored signs
 // replace the nonlinearity (gradient of lrelu + clamp).
 // G: planes per wave.  2 = packed mode for narrow planes (yW <= PACKTW, one strip): lanes 0-31 work on plane 2k, lanes 32-63 on plane
@@ -306,11 +326,14 @@ struct Stream {
         }
     }
 
-    // one input row: H-up into window slot S, then U upsampled rows through lrelu into the down accumulators
-    template <int S>
+    // one input row: H-up into window slot S, then U upsampled rows through lrelu into the down accumulators.  FAST (plain forward
+    // only): the activation is the single med3(u, slope u, clamp), and `liveGain` drops to 0 from the row in which a staged sample
+    // failed |x| <= fastT (the outputs of such a pass are rewritten by a pass with FAST = false)
+    template <int S, bool FAST>
     static __device__ __forceinline__ void step(State& st, const StreamParams& p, const T* __restrict__ plane, T* __restrict__ oplane,
                                                 unsigned char* __restrict__ splane, lds_f* sIn, lds_f* sOut, int i, int delta, int lane,
-                                                int oy0, int oy1, int ox0, int oxN, bool pairStore, float& liveGain, float& liveGain1, bool wide) {
+                                                int oy0, int oy1, int ox0, int oxN, bool pairStore, float& liveGain, float& liveGain1, bool wide,
+                                                float fastT) {
         constexpr bool RDOWN = RADIAL == 1 || RADIAL == 2 || RADIAL >= 5;   // full 12x12 DOWN filter (config R forward)
         constexpr bool FOLD = RADIAL >= 5;                         // ... whose rows read the same in both directions
         constexpr bool UP2D = RADIAL == 3 || RADIAL == 4;          // full 12x12 UP filter (adjoint of those layers)
@@ -327,7 +350,18 @@ struct Stream {
         // scalar register, overwritten in place -- is NaN: every output it still writes in this strip is NaN.  That is a superset of the
         // reference's NaN footprint (a failure stays loud and stays where it happened), at no cost inside the nonlinearity.  The
         // last load of a row holds the strip's 6 halo samples, which the neighbouring strip classifies as its own: left out here.
-        if (SIGNS == 0 && SG3_NAN_GUARD && G > 1) {
+        if (SIGNS == 0 && FAST) {
+            // fast pass: every load a lane stages, the strip's halo included (it feeds this strip's upsampled samples), is tested
+            // against the threshold: v_cmp_nle is true for |x| > T, NaN and infinity alike, and takes the place of the class test.
+            // The radial forms have no scalar register to spare (a spill puts v_readlane into the row loop): T sits in a VGPR there.
+#pragma unroll
+            for (int q = 0; q < Cfg::NL; q++) {
+                unsigned long long m;
+                if (RADIAL) asm("v_cmp_nle_f32_e64 %0, |%1|, %2" : "=s"(m) : "v"(st.pre[PS][q]), "v"(fastT));
+                else        asm("v_cmp_nle_f32_e64 %0, |%1|, %2" : "=s"(m) : "v"(st.pre[PS][q]), "s"(fastT));
+                liveGain = m != 0ull ? 0.f : liveGain;
+            }
+        } else if (SIGNS == 0 && SG3_NAN_GUARD && G > 1) {
             // packed: every load is the wave's own (no neighbouring strip); staging lane e = lane + 64 q belongs to the first plane
             // while e < PSEG -- each plane has its own gain register
 #pragma unroll
@@ -383,7 +417,8 @@ struct Stream {
         // ---- U new upsampled rows ----
         const float slope = p.slope, clampv = p.clamp / p.gain, gain = p.gain;
         // sign-write mode applies the gain before the nonlinearity; the 2-D up filter's taps carry no up^2 factor
-        const float gainOut = (SIGNS == 1) ? 1.f : (UP2D ? p.gain * (float)(U * U) : ((SIGNS == 0 && SG3_NAN_GUARD) ? ((G > 1 && lane >= 32) ? liveGain1 : liveGain) : p.gain));
+        const float gainOut = (SIGNS == 1) ? 1.f : (UP2D ? p.gain * (float)(U * U) :
+                              ((SIGNS == 0 && (SG3_NAN_GUARD || FAST)) ? ((G > 1 && lane >= 32 && !FAST) ? liveGain1 : liveGain) : p.gain));
 #pragma unroll
         for (int j = 0; j < U; j++) {
             const int kv = U - 1 - j;                          // vertical up phase of this row
@@ -470,6 +505,12 @@ struct Stream {
                     const __amdgpu_buffer_rsrc_t ss = __builtin_amdgcn_make_buffer_rsrc((void*)(splane + (long long)sr * p.sWb), (short)0, p.sWb, 0x00020000);
                     __builtin_amdgcn_raw_buffer_store_b8((unsigned char)byte, ss, bofs, 0, 0);
                 }
+            } else if (FAST) {
+                // lrelu + clamp in one instruction: med3(u, slope u, c) = med3(max(u, slope u), -c, c) whenever slope |u| <= c (u < 0:
+                // slope u; 0 <= u <= c: u; u > c: c -- exact selections), which the threshold test on the staged samples guarantees
+                const v2f s0 = u0 * splat(slope), s1 = u1 * splat(slope);
+                a[0] = __builtin_amdgcn_fmed3f(u0.x, s0.x, clampv); a[1] = __builtin_amdgcn_fmed3f(u0.y, s0.y, clampv);
+                a[2] = __builtin_amdgcn_fmed3f(u1.x, s1.x, clampv); a[3] = __builtin_amdgcn_fmed3f(u1.y, s1.y, clampv);
             } else {
                 // leaky ReLU (slope <= 1 so lrelu(v) = max(v, slope*v)) and clamp.  The activation gain g > 0 commutes with
                 // both: clamp_c(lrelu(g*u)) = g * clamp_{c/g}(lrelu(u)), so g is applied once per OUTPUT sample after the
@@ -650,6 +691,40 @@ struct Stream {
         }
     }
 
+    // the chunk: zero window and accumulators, prefetch, then the rows 6 at a time
+    template <bool FAST>
+    static __device__ __forceinline__ void stream_chunk(State& st, const StreamParams& p, const T* __restrict__ plane, T* __restrict__ oplane,
+                                                        unsigned char* __restrict__ splane, lds_f* sIn, lds_f* sOut, int iFirst, int nBlocks,
+                                                        int delta, int lane, int oy0, int oy1, int ox0, int oxN, bool pairStore, float& liveGain,
+                                                        float& liveGain1, bool wide, float fastT) {
+#pragma unroll
+        for (int s = 0; s < 6; s++) {
+            st.w[s][0] = splat(0.f); st.w[s][1] = splat(0.f);
+#pragma unroll
+            for (int q = 0; q < 4; q++) st.xw[s][q] = splat(0.f);
+            st.acc[s][0] = splat(0.f); st.acc[s][1] = splat(0.f);
+            if (s < SG3_PREFETCH_ROWS) prefetch(st, s, p, plane, splane, iFirst + s);
+        }
+
+        int i = iFirst;
+        for (int blk = 0; blk < nBlocks; blk++, i += 6) {
+            step<0, FAST>(st, p, plane, oplane, splane, sIn, sOut, i + 0, delta, lane, oy0, oy1, ox0, oxN, pairStore, liveGain, liveGain1, wide, fastT);
+            step<1, FAST>(st, p, plane, oplane, splane, sIn, sOut, i + 1, delta, lane, oy0, oy1, ox0, oxN, pairStore, liveGain, liveGain1, wide, fastT);
+            step<2, FAST>(st, p, plane, oplane, splane, sIn, sOut, i + 2, delta, lane, oy0, oy1, ox0, oxN, pairStore, liveGain, liveGain1, wide, fastT);
+            step<3, FAST>(st, p, plane, oplane, splane, sIn, sOut, i + 3, delta, lane, oy0, oy1, ox0, oxN, pairStore, liveGain, liveGain1, wide, fastT);
+            step<4, FAST>(st, p, plane, oplane, splane, sIn, sOut, i + 4, delta, lane, oy0, oy1, ox0, oxN, pairStore, liveGain, liveGain1, wide, fastT);
+            step<5, FAST>(st, p, plane, oplane, splane, sIn, sOut, i + 5, delta, lane, oy0, oy1, ox0, oxN, pairStore, liveGain, liveGain1, wide, fastT);
+            if ((6 * U / D) % 6 != 0) {
+                // a trip completes 6U/D output rows; when that is 3 (U = 2, D = 4) the ring of output rows has turned by
+                // half: swap the halves so that the compile-time slot numbering holds for the next trip
+#pragma unroll
+                for (int r = 0; r < 3; r++)
+#pragma unroll
+                    for (int h = 0; h < 2; h++) { const v2f t = st.acc[r][h]; st.acc[r][h] = st.acc[r + 3][h]; st.acc[r + 3][h] = t; }
+            }
+        }
+    }
+
     static __device__ __forceinline__ void run(const StreamParams& p) {
         static_assert((D == 2 || D == 4) && (6 * U) % D == 0, "streaming kernel: down is 2 or 4");
         constexpr bool RDOWN = RADIAL == 1 || RADIAL == 2 || RADIAL >= 5;
@@ -773,32 +848,24 @@ struct Stream {
         const int iLast = ceil_div_s(uyB - p.py0, U) + 5;       // step that yields uyB
         const int nBlocks = (iLast - iFirst + 1 + 5) / 6;
 
-#pragma unroll
-        for (int s = 0; s < 6; s++) {
-            st.w[s][0] = splat(0.f); st.w[s][1] = splat(0.f);
-#pragma unroll
-            for (int q = 0; q < 4; q++) st.xw[s][q] = splat(0.f);
-            st.acc[s][0] = splat(0.f); st.acc[s][1] = splat(0.f);
-            if (s < SG3_PREFETCH_ROWS) prefetch(st, s, p, plane, splane, iFirst + s);
-        }
-
-        int i = iFirst;
-        for (int blk = 0; blk < nBlocks; blk++, i += 6) {
-            step<0>(st, p, plane, oplane, splane, sIn, sOut, i + 0, delta, lane, oy0, oy1, ox0, oxN, pairStore, liveGain, liveGain1, wide);
-            step<1>(st, p, plane, oplane, splane, sIn, sOut, i + 1, delta, lane, oy0, oy1, ox0, oxN, pairStore, liveGain, liveGain1, wide);
-            step<2>(st, p, plane, oplane, splane, sIn, sOut, i + 2, delta, lane, oy0, oy1, ox0, oxN, pairStore, liveGain, liveGain1, wide);
-            step<3>(st, p, plane, oplane, splane, sIn, sOut, i + 3, delta, lane, oy0, oy1, ox0, oxN, pairStore, liveGain, liveGain1, wide);
-            step<4>(st, p, plane, oplane, splane, sIn, sOut, i + 4, delta, lane, oy0, oy1, ox0, oxN, pairStore, liveGain, liveGain1, wide);
-            step<5>(st, p, plane, oplane, splane, sIn, sOut, i + 5, delta, lane, oy0, oy1, ox0, oxN, pairStore, liveGain, liveGain1, wide);
-            if ((6 * U / D) % 6 != 0) {
-                // a trip completes 6U/D output rows; when that is 3 (U = 2, D = 4) the ring of output rows has turned by
-                // half: swap the halves so that the compile-time slot numbering holds for the next trip
-#pragma unroll
-                for (int r = 0; r < 3; r++)
-#pragma unroll
-                    for (int h = 0; h < 2; h++) { const v2f t = st.acc[r][h]; st.acc[r][h] = st.acc[r + 3][h]; st.acc[r + 3][h] = t; }
+        // Plain forward: the chunk runs first with the one-instruction activation, every staged sample tested against the threshold
+        // (a wave-uniform choice made once, before the row loop: a branch inside it costs 5 %); a wave that met a sample above it --
+        // or a NaN, or an infinity -- runs the chunk again with lrelu + clamp and the NaN guard, rewriting every output it stored.
+        // Either way the outputs are those of the second form, bit for bit.
+        // The fast pass's output gain is its flag (0 from the row of a failed test on; fastAct promises a finite positive gain).
+        bool slow = true;
+        if constexpr (SIGNS == 0) {
+            const float fastT = p.fastAct ? to_sgpr(fast_threshold(p.fu, Cfg::FU, U, p.gain, p.slope, p.clamp)) : -1.f;
+            if (fastT > 0.f) {
+                float fastGain = p.gain, unused = p.gain;
+                stream_chunk<true>(st, p, plane, oplane, splane, sIn, sOut, iFirst, nBlocks, delta, lane, oy0, oy1, ox0, oxN, pairStore, fastGain,
+                                   unused, wide, fastT);
+                slow = fastGain != p.gain;
             }
         }
+        if (slow)
+            stream_chunk<false>(st, p, plane, oplane, splane, sIn, sOut, iFirst, nBlocks, delta, lane, oy0, oy1, ox0, oxN, pairStore, liveGain, liveGain1,
+                                wide, -1.f);
 #ifdef SG3_STAMPS
         if (p.stamps && lane == 0) {
             p.stamps[2 * (long long)blockIdx.x] = __builtin_amdgcn_s_memtime() - stampC;
@@ -916,6 +983,14 @@ static bool stream_packs_planes(const sg3_filtered_lrelu_params& q, int width) {
            (xsC + q.xW) * esz < 0x7fffffffLL && (ysC + q.yW) * esz < 0x7fffffffLL;
 }
 
+// The one-instruction activation of the plain forward (StreamParams.fastAct): for a finite positive gain and a clamp that is a number.
+// SG3_FLRELU_SLOWACT=1 in the environment keeps lrelu + clamp everywhere (A/B timing and the parity tests; read on every call, so
+// that a test can compare both forms in one process).
+static bool stream_fast_activation(const sg3_filtered_lrelu_params& q) {
+    const char* e = getenv("SG3_FLRELU_SLOWACT");
+    return !(e && e[0] == '1') && !q.readSigns && !q.writeSigns && q.gain > 0.f && q.gain < INFINITY && q.clamp >= 0.f;
+}
+
 // width of the full strips when a row is cut into full strips + a packed remainder, and their number (0: equal strips instead --
 // no remainder, a remainder too wide to pack, or more waves than equal strips take)
 constexpr int STREAM_FULL_TW = 120;
@@ -961,6 +1036,7 @@ static int launch_stream(const sg3_filtered_lrelu_params& q, hipStream_t st) {
     p.bStride = q.bStride;
     p.px0 = q.px0; p.py0 = q.py0;
     p.gain = q.gain; p.slope = q.slope; p.clamp = q.clamp; p.flip = q.flip;
+    p.fastAct = stream_fast_activation(q) ? 1 : 0;
 
     p.s = q.s; p.sH = q.sH; p.sWb = q.sWbytes; p.sx = q.sx; p.sy = q.sy;
     p.ysum = q.ySumPartial;
@@ -1121,6 +1197,11 @@ int sg3_filtered_lrelu_shape(int xH, int xW, int up, int down, int fuW, int fuH,
     if (sWbytes) *sWbytes = (int)(sw >> 2);
     if (swLimit) *swLimit = (int)((sw_active + 3) >> 2);
     return SG3_OK;
+}
+
+float sg3_filtered_lrelu_fast_threshold(const float* fu, int fuW, int up, float gain, float slope, float clamp) {
+    if (!fu || up < 1 || fuW < up) return -1.f;
+    return sg3::fast_threshold(fu, fuW, up, gain, slope, clamp);
 }
 
 int sg3_filtered_lrelu_planes_per_wave(const sg3_filtered_lrelu_params* p) {
