@@ -465,8 +465,13 @@ SG3_API int sg3_conv2d_wgrad(const sg3_wgrad_params* p, void* stream);
  *            (an eval-mode BatchNorm in FRONT of the convolution, helpers.py:108);
  *   a BatchNorm BEHIND the convolution is folded into w / bias by the caller.
  *   act: 0 none, 1 PReLU with per-channel slope[o], 2 leaky ReLU with slope[0].
- * Exact fp32 matrix-core arithmetic (v_mfma_f32_32x32x2_f32), NCHW contiguous
- * fp32 tensors, k in {1,3}, stride in {1,2}.
+ * NCHW contiguous fp32 tensors, k in {1,3}, stride in {1,2}, pad 0 .. k/2 + 1.
+ * SG3_CONV_FP32: exact fp32 matrix-core arithmetic (v_mfma_f32_32x32x2_f32).
+ * SG3_CONV_F16X3: operands split into fp16 hi + lo.  Activations keep relative
+ *   2^-21 plus up to ~2^-23 absolute (below |x| = 2^-3 the halves leave fp16's
+ *   normal range; they are not rescaled).  Weights are lifted per output channel
+ *   by a power of two at packing (wScale holds the inverse, applied exactly in the
+ *   epilogue) and keep relative 2^-22 within 2^-17 of their channel's maximum.
  * wPacked comes from sg3_conv2d_pack (layout [O][ceil(I/KC)][k*k][KC]).
  * ---------------------------------------------------------------------- */
 typedef struct sg3_conv2d_params {
@@ -480,15 +485,24 @@ typedef struct sg3_conv2d_params {
     int32_t        N, I, O, H, W;
     int32_t        k, stride, pad;
     int32_t        act;
-    int32_t        precision;  /* SG3_CONV_FP32 (exact) | SG3_CONV_F16X3 (1x1 / 3x3, stride 1 or 2: fp16 x 3 split, fp32-equivalent) */
+    int32_t        precision;  /* SG3_CONV_FP32 (exact) | SG3_CONV_F16X3 (1x1 / 3x3, stride 1 or 2: fp16 x 3 split, precision above) */
     int32_t*       rangeFlag;  /* f16x3: device int, OR-ed with 1 when an operand left the fp16 range (the result of that
                                 * call is then invalid and the caller repeats it with SG3_CONV_FP32); never cleared here */
+    const float*   wScale;     /* f16x3: [O], written by sg3_conv2d_pack with wPacked; ignored for SG3_CONV_FP32 */
 } sg3_conv2d_params;
 
 SG3_API int sg3_conv2d(const sg3_conv2d_params* p, void* stream);
 
-/* w [O,I,k,k] (* outScale[o] when given: a folded BatchNorm) -> packed layout */
-SG3_API int sg3_conv2d_pack(const float* w, const float* outScale, float* wPacked, int O, int I, int k, int precision, void* stream);
+/* Diagnostic: the kernel form sg3_conv2d launches for *p (same checks, nothing launched; negative status for invalid params).
+ *   SG3_CONV_FP32:  ((k == 3) * 2 + (stride == 2)) * 3 + tile, tile 0 = 128 ch x 4 rows, 1 = 64 ch x 2 rows, 2 = 32 ch x 4 rows
+ *                   (12 forms);
+ *   SG3_CONV_F16X3: SG3_CONV2D_FORM_F16X3 + 0 (1x1 stride 2), 1 (1x1 stride 1), 2 (3x3 stride 2), 3 (3x3 stride 1, outH <= 16,
+ *                   4-row tile), 4 (3x3 stride 1, 4-row tile: fewer 8-row tiles than two per CU), 5 (3x3 stride 1, 8-row tile). */
+#define SG3_CONV2D_FORM_F16X3 16
+SG3_API int sg3_conv2d_form(const sg3_conv2d_params* p);
+
+/* w [O,I,k,k] (* outScale[o] when given: a folded BatchNorm) -> packed layout; SG3_CONV_F16X3 also writes wScale [O] */
+SG3_API int sg3_conv2d_pack(const float* w, const float* outScale, float* wPacked, float* wScale, int O, int I, int k, int precision, void* stream);
 
 /* ------------------------------------------------------------------------
  * modulation_backward -- dL/dw and dL/ds of modulated_conv2d's per-sample effective weights, given G = dL/dw_eff
@@ -562,14 +576,17 @@ SG3_API int sg3_unfold3x3s2(const sg3_unfold_params* p, void* stream);
  * stride-2 convolutions of levels 2.. as GEMMs over unfolded patches, and the closing EqualLinear, models/stylegan2/model.py
  * EqualLinear.forward; restyle_psp_encoders.py:26-50 runs n_styles heads):
  *     c[g][m][n] = sum_k lrelu(a[g][m][k], slope) * w[g][k][n] + bias[g][n]
- *   float32 in and out, split-precision fp16 x 3 arithmetic on the matrix cores (fp32-equivalent), weight-bandwidth bound.
+ *   float32 in and out, split-precision fp16 x 3 arithmetic on the matrix cores, weight-bandwidth bound; operand precision as
+ *   for sg3_conv2d's SG3_CONV_F16X3 (weights: relative 2^-21 within 2^-17 of their column's maximum).
  *   sg3_head_gemm_pack writes w ([G][K][N] float32, K % 16 == 0, N % 32 == 0) as matrix-instruction fragments into `packed`
- *   (sg3_head_gemm_packed_halfs(G,K,N) fp16 elements, -1 for unsupported shapes); *rangeFlag is OR-ed with 1 when a weight
- *   (pack) or an activation (gemm) lies outside the fp16 range: the caller then uses its fp32 path.  bias may be NULL.
+ *   (sg3_head_gemm_packed_halfs(G,K,N) fp16 elements, -1 for unsupported shapes), every column lifted by a power of two, and the
+ *   inverse powers into colScale ([G][N] float32); *rangeFlag is OR-ed with 1 when a weight (pack) or an activation (gemm) lies
+ *   outside the fp16 range: the caller then uses its fp32 path.  bias may be NULL.
  * ---------------------------------------------------------------------- */
 typedef struct sg3_head_gemm_params {
     const float*   a;              /* [G][M][K] dense */
     const void*    wPacked;        /* from sg3_head_gemm_pack */
+    const float*   colScale;       /* [G][N], from sg3_head_gemm_pack with wPacked */
     const float*   bias;           /* [G][N] or NULL */
     float*         c;              /* [G][M][N] dense */
     int32_t*       rangeFlag;
@@ -578,7 +595,7 @@ typedef struct sg3_head_gemm_params {
 } sg3_head_gemm_params;
 
 SG3_API long long sg3_head_gemm_packed_halfs(int32_t G, int32_t K, int32_t N);
-SG3_API int sg3_head_gemm_pack(const float* w, void* packed, int32_t G, int32_t K, int32_t N, int32_t* rangeFlag, void* stream);
+SG3_API int sg3_head_gemm_pack(const float* w, void* packed, float* colScale, int32_t G, int32_t K, int32_t N, int32_t* rangeFlag, void* stream);
 SG3_API int sg3_head_gemm(const sg3_head_gemm_params* p, void* stream);
 
 /* ----------------------------------------------------------------------

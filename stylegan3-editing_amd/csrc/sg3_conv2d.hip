@@ -18,6 +18,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct PlainConvParams {
     const float* x; const float* wp; const float* inScale; const float* inShift; const float* bias; const float* slope; float* out;
+    const float* wScale;                    // f16x3: per output channel, the inverse of the power of two the pack applied
     int N, I, O, H, W, outH, outW, stride, pad, act;
     int nch, xTiles, yTiles, mTiles, totalBlocks;
 };
@@ -181,12 +182,17 @@ conv2d_pack_kernel(const float* w, const float* outScale, float* wp, int O, int 
 // Split-precision form for the 3x3 convolutions (stride 1: the backbone's FLOPs; stride 2: the first unit of every stage, the
 // ResNet34 blocks, with the patch columns de-interleaved in LDS so that the stride-2 im2col read stays conflict-free) (same arithmetic as
 // modconv_f16x3_kernel in sg3_modconv.hip: x = hi + lo in fp16, Ah*Bh + Ah*Bl + Al*Bh on v_mfma_f32_32x32x16_f16, fp32
-// accumulation, fp32-equivalent).  No bound on BatchNorm-ed activations is known ahead of time and none is needed for
-// accuracy (fp16's exponent range covers 6e-5 .. 65504 at full split precision, smaller magnitudes lose only bits that
-// are below 1e-11 absolute); what must not happen silently is overflow, so every workgroup tracks max |operand| while
-// staging and raises `*flag` when it exceeds the fp16 range -- the caller then repeats the layer stack on the exact
-// fp32 kernel (torch_utils/ops/plain_conv.py).  Weights are packed [O][I/16][tap][hi|lo][16] halfs by
-// conv2d_pack_f16x3_kernel with the folded BatchNorm scale applied before the split.
+// accumulation).  Precision per operand (tests/split_model.py models both splits bit for bit):
+//   * activations (split2: hi truncated to 11 bits, lo rounded toward zero): relative 2^-21 where both halves are normal fp16
+//     numbers; lo falls below 2^-14 (onto fp16's absolute 2^-24 grid) for |x| < 2^-3, and a hi below 2^-14 loses bits lo does not
+//     recover, so an activation carries up to ~2^-23 ABSOLUTE error besides.  No bound on BatchNorm-ed activations is known
+//     ahead of time, so they are not rescaled;
+//   * weights: packed [O][I/16][tap][hi|lo][16] halfs by conv2d_pack_f16x3_kernel with the folded BatchNorm scale applied and
+//     then every output channel lifted by a power of two into [2^14, 2^15) (pow2_lift, scale up only), rounded to nearest:
+//     relative 2^-22 for every weight within 2^-17 of its channel's maximum, whatever that maximum is.  The epilogue multiplies
+//     the inverse power (wScale[o], exact) into the fp32 accumulator before bias and activation.
+// What must not happen silently is overflow, so every workgroup tracks max |operand| while staging and raises `*flag` when it
+// exceeds the fp16 range -- the caller then repeats the layer stack on the exact fp32 kernel (torch_utils/ops/plain_conv.py).
 template <int KS, int STRIDE, int WM, int WN, int TM, int TN>
 __global__ void __launch_bounds__(256, (TM * TN <= 4) ? 2 : 1)
 conv2d_f16x3_kernel(PlainConvParams p, int* flag) {
@@ -389,11 +395,12 @@ conv2d_f16x3_kernel(PlainConvParams p, int* flag) {
 #pragma unroll
         for (int a = 0; a < TM; a++) {
             const int oL = o0 + (wm * TM + a) * 32 + 4 * lh;
-            float bv[16], sl[16];
+            float bv[16], sl[16], ws[16];
 #pragma unroll
             for (int r = 0; r < 16; r++) {
                 const int o = min(oL + (r & 3) + 8 * (r >> 2), p.O - 1);                // channels beyond O are dropped by the store
                 bv[r] = p.bias ? p.bias[o] : 0.f;
+                ws[r] = p.wScale[o];
                 sl[r] = p.act == 1 ? p.slope[o] : (p.act == 2 ? p.slope[0] : 1.f);
             }
             const unsigned laneBase = gx < p.outW ? (unsigned)oL * planeB + (unsigned)gx * 4u : 0x80000000u;
@@ -404,7 +411,7 @@ conv2d_f16x3_kernel(PlainConvParams p, int* flag) {
                 const unsigned rowOff = laneBase + (unsigned)(gy * p.outW) * 4u;
 #pragma unroll
                 for (int r = 0; r < 16; r++) {
-                    float v = acc[a][b][r] + bv[r];
+                    float v = acc[a][b][r] * ws[r] + bv[r];
                     if (p.act) v = v < 0.f ? v * sl[r] : v;
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), orr, (int)(rowOff + (unsigned)((r & 3) + 8 * (r >> 2)) * planeB), 0, 0);
                 }
@@ -420,11 +427,12 @@ conv2d_f16x3_kernel(PlainConvParams p, int* flag) {
             if (o >= p.O) continue;
             const float bv = p.bias ? p.bias[o] : 0.f;
             const float sl = p.act == 1 ? p.slope[o] : (p.act == 2 ? p.slope[0] : 1.f);
+            const float ws = p.wScale[o];
 #pragma unroll
             for (int b = 0; b < TN; b++) {
                 const int gy = y0 + wn * TN + b;
                 if (gy < p.outH && gx < p.outW) {
-                    float v = acc[a][b][r] + bv;
+                    float v = acc[a][b][r] * ws + bv;
                     if (p.act) v = v < 0.f ? v * sl : v;
                     outp[((size_t)o * p.outH + gy) * p.outW + gx] = v;
                 }
@@ -433,14 +441,26 @@ conv2d_f16x3_kernel(PlainConvParams p, int* flag) {
 }
 
 __global__ void __launch_bounds__(256)
-conv2d_pack_f16x3_kernel(const float* w, const float* outScale, float* wp, int O, int I, int nch, int taps) {
+conv2d_pack_f16x3_kernel(const float* w, const float* outScale, float* wp, float* wScale, int O, int I, int nch, int taps) {
+    __shared__ float red[256];
     const int o = blockIdx.x;
     const float sc = outScale ? outScale[o] : 1.f;
+    const float* src = w + (size_t)o * I * taps;
+    float peak = 0.f;
+    for (int j = threadIdx.x; j < I * taps; j += 256) peak = fmaxf(peak, fabsf(src[j] * sc));
+    red[threadIdx.x] = peak;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s]);
+        __syncthreads();
+    }
+    const float lift = pow2_lift(red[0]);                    // exact: the folded weight times a power of two
+    if (threadIdx.x == 0) wScale[o] = 1.f / lift;
     _Float16* dst = reinterpret_cast<_Float16*>(wp) + (size_t)o * nch * taps * 32;
     for (int j = threadIdx.x; j < nch * taps * 16; j += 256) {
         const int c = j % 16, t = (j / 16) % taps, ch = j / (16 * taps);
         const int i = ch * 16 + c;
-        const float v = i < I ? w[((size_t)o * I + i) * taps + t] * sc : 0.f;
+        const float v = i < I ? (src[(size_t)i * taps + t] * sc) * lift : 0.f;
         const _Float16 h = (_Float16)v;
         _Float16* d = dst + ((size_t)ch * taps + t) * 32 + c;
         d[0] = h;
@@ -466,6 +486,7 @@ static int launch_plain_f16x3(const sg3_conv2d_params& q, hipStream_t st) {
     constexpr size_t ldsBytes = ((size_t)BM * (KS * KS * 32 + 8) + 4 * (size_t)((ROWS - 1) * STRIDE + KS) * (31 * STRIDE + KS) * 8) * sizeof(_Float16);
     PlainConvParams p;
     p.x = q.x; p.wp = q.wPacked; p.inScale = q.inScale; p.inShift = q.inShift; p.bias = q.bias; p.slope = q.slope; p.out = q.out;
+    p.wScale = q.wScale;
     p.N = q.N; p.I = q.I; p.O = q.O; p.H = q.H; p.W = q.W; p.stride = STRIDE; p.pad = q.pad; p.act = q.act;
     p.outH = (q.H + 2 * q.pad - KS) / STRIDE + 1; p.outW = (q.W + 2 * q.pad - KS) / STRIDE + 1;
     p.nch = ceil_div(q.I, 16);
@@ -481,19 +502,29 @@ static int launch_plain_f16x3(const sg3_conv2d_params& q, hipStream_t st) {
     return SG3_OK;
 }
 
-static int dispatch_plain_f16x3(const sg3_conv2d_params& q, hipStream_t st) {
-    if (q.k == 1)                                                                    // the projection shortcuts: same kernel, one tap
-        return q.stride == 2 ? launch_plain_f16x3<1, 2, 1, 4, 2, 1>(q, st) : launch_plain_f16x3<1, 1, 1, 4, 2, 1>(q, st);
-    if (q.stride == 2) return launch_plain_f16x3<3, 2, 1, 4, 2, 1>(q, st);        // 64 x (4 rows x 32), 9 x 65 patch
+// The branch of dispatch_plain_f16x3 a call takes (SG3_CONV2D_FORM_F16X3 + 0 .. 5, see sg3_conv2d_form)
+static int plain_f16x3_form(const sg3_conv2d_params& q) {
+    if (q.k == 1) return q.stride == 2 ? 0 : 1;                                     // the projection shortcuts: same kernel, one tap
+    if (q.stride == 2) return 2;                                                     // 64 x (4 rows x 32), 9 x 65 patch
     const int outH = q.H + 2 * q.pad - 2, outW = q.W + 2 * q.pad - 2;
-    if (outH <= 16) return launch_plain_f16x3<3, 1, 1, 4, 2, 1>(q, st);           // 64 x (4 rows x 32): the 16x16 maps
+    if (outH <= 16) return 3;                                                        // 64 x (4 rows x 32): the 16x16 maps
     // The 8-row tile (230 registers: two workgroups per CU) needs a grid that offers every CU its two workgroups; the 32 x 32 maps
     // of a 16-frame batch (14 units of the IR-SE50 trunk, 28 launches) give 256 eight-row tiles = ONE four-wave workgroup per CU
     // (counters, round 4: 0.85 waves per SIMD, matrix pipes 0.32 busy at 2.45 GHz -- latency, not power).  Such grids take the
     // 4-row tile instead (153 registers, three workgroups per CU): twice the workgroups, each with half the rows.
     const long long tiles8 = (long long)q.N * ceil_div(q.O, 64) * ceil_div(outH, 8) * ceil_div(outW, 32);
-    if (tiles8 < 2 * (long long)device_cu_count()) return launch_plain_f16x3<3, 1, 1, 4, 2, 1>(q, st);
-    return launch_plain_f16x3<3, 1, 1, 4, 2, 2>(q, st);                           // 64 x (8 rows x 32)
+    if (tiles8 < 2 * (long long)device_cu_count()) return 4;
+    return 5;                                                                        // 64 x (8 rows x 32)
+}
+
+static int dispatch_plain_f16x3(const sg3_conv2d_params& q, hipStream_t st) {
+    switch (plain_f16x3_form(q)) {
+    case 0: return launch_plain_f16x3<1, 2, 1, 4, 2, 1>(q, st);
+    case 1: return launch_plain_f16x3<1, 1, 1, 4, 2, 1>(q, st);
+    case 2: return launch_plain_f16x3<3, 2, 1, 4, 2, 1>(q, st);
+    case 3: case 4: return launch_plain_f16x3<3, 1, 1, 4, 2, 1>(q, st);
+    default: return launch_plain_f16x3<3, 1, 1, 4, 2, 2>(q, st);
+    }
 }
 
 template <int KS, int STRIDE, int WM, int WN, int TM, int TN>
@@ -501,6 +532,7 @@ static int launch_plain(const sg3_conv2d_params& q, hipStream_t st) {
     constexpr int BM = WM * TM * 32, ROWS = WN * TN, KC = (KS == 3) ? 8 : 16;
     PlainConvParams p;
     p.x = q.x; p.wp = q.wPacked; p.inScale = q.inScale; p.inShift = q.inShift; p.bias = q.bias; p.slope = q.slope; p.out = q.out;
+    p.wScale = q.wScale;
     p.N = q.N; p.I = q.I; p.O = q.O; p.H = q.H; p.W = q.W; p.stride = q.stride; p.pad = q.pad; p.act = q.act;
     p.outH = (q.H + 2 * q.pad - KS) / STRIDE + 1; p.outW = (q.W + 2 * q.pad - KS) / STRIDE + 1;
     p.nch = ceil_div(q.I, KC);
@@ -513,25 +545,35 @@ static int launch_plain(const sg3_conv2d_params& q, hipStream_t st) {
     return SG3_OK;
 }
 
+// The tile of dispatch_plain a call takes: small feature maps (16x16 and below) get the 4-row tile, large ones the 128-channel
+// tile when O allows
+static int plain_tile(const sg3_conv2d_params& q) {
+    const int outH = (q.H + 2 * q.pad - q.k) / q.stride + 1;
+    if (q.O >= 128 && outH >= 8) return 0;                                   // 128 x (4 rows x 32)
+    if (q.O > 32) return 1;                                                  // 64 x (2 rows x 32)
+    return 2;                                                                // 32 x (4 rows x 32)
+}
+
 template <int KS, int STRIDE>
 static int dispatch_plain(const sg3_conv2d_params& q, hipStream_t st) {
-    // small feature maps (16x16 and below) get the 4-row tile, large ones the 128-channel tile when O allows
-    const int outH = (q.H + 2 * q.pad - KS) / STRIDE + 1;
-    if (q.O >= 128 && outH >= 8) return launch_plain<KS, STRIDE, 2, 2, 2, 2>(q, st);
-    if (q.O > 32) return launch_plain<KS, STRIDE, 2, 2, 1, 1>(q, st);          // 64 x (2 rows x 32)
-    return launch_plain<KS, STRIDE, 1, 4, 1, 1>(q, st);                        // 32 x (4 rows x 32)
+    switch (plain_tile(q)) {
+    case 0: return launch_plain<KS, STRIDE, 2, 2, 2, 2>(q, st);
+    case 1: return launch_plain<KS, STRIDE, 2, 2, 1, 1>(q, st);
+    default: return launch_plain<KS, STRIDE, 1, 4, 1, 1>(q, st);
+    }
 }
 
 } // namespace sg3
 
 extern "C" {
 
-int sg3_conv2d_pack(const float* w, const float* outScale, float* wPacked, int O, int I, int k, int precision, void* stream) {
+int sg3_conv2d_pack(const float* w, const float* outScale, float* wPacked, float* wScale, int O, int I, int k, int precision, void* stream) {
     using namespace sg3;
     SG3_REQUIRE(w && wPacked && O > 0 && I > 0 && (k == 1 || k == 3), "conv2d_pack: bad arguments");
     SG3_REQUIRE(precision == SG3_CONV_FP32 || precision == SG3_CONV_F16X3, "conv2d_pack: bad precision");
     if (precision == SG3_CONV_F16X3) {
-        hipLaunchKernelGGL(conv2d_pack_f16x3_kernel, dim3(O), dim3(256), 0, (hipStream_t)stream, w, outScale, wPacked, O, I, ceil_div(I, 16), k * k);
+        SG3_REQUIRE(wScale, "conv2d_pack: the f16x3 form writes per-channel scales (wScale)");
+        hipLaunchKernelGGL(conv2d_pack_f16x3_kernel, dim3(O), dim3(256), 0, (hipStream_t)stream, w, outScale, wPacked, wScale, O, I, ceil_div(I, 16), k * k);
         SG3_LAUNCH_CHECK("conv2d_pack_f16x3_kernel");
         return SG3_OK;
     }
@@ -541,7 +583,7 @@ int sg3_conv2d_pack(const float* w, const float* outScale, float* wPacked, int O
     return SG3_OK;
 }
 
-int sg3_conv2d(const sg3_conv2d_params* p, void* stream) {
+static int check_conv2d(const sg3_conv2d_params* p) {
     using namespace sg3;
     SG3_REQUIRE(p && p->x && p->wPacked && p->out, "conv2d: null tensor");
     SG3_REQUIRE(p->N > 0 && p->I > 0 && p->O > 0 && p->H > 0 && p->W > 0, "conv2d: empty tensor");
@@ -551,13 +593,30 @@ int sg3_conv2d(const sg3_conv2d_params* p, void* stream) {
     SG3_REQUIRE(p->act >= 0 && p->act <= 2, "conv2d: act must be 0, 1 or 2");
     SG3_REQUIRE(p->act == 0 || p->slope, "conv2d: slope missing");
     SG3_REQUIRE(p->H + 2 * p->pad >= p->k && p->W + 2 * p->pad >= p->k, "conv2d: empty output");
-    hipStream_t st = (hipStream_t)stream;
     if (p->precision == SG3_CONV_F16X3) {
         SG3_REQUIRE(p->rangeFlag, "conv2d: the f16x3 form takes a range flag");
+        SG3_REQUIRE(p->wScale, "conv2d: the f16x3 form takes the per-channel weight scales of its pack");
         SG3_REQUIRE((int64_t)p->I * p->H * p->W * 4 < (int64_t)1 << 31, "conv2d: f16x3 needs a sample below 2 GiB (32-bit offsets)");
-        return dispatch_plain_f16x3(*p, st);
+        return SG3_OK;
     }
     SG3_REQUIRE(p->precision == SG3_CONV_FP32, "conv2d: bad precision");
+    return SG3_OK;
+}
+
+int sg3_conv2d_form(const sg3_conv2d_params* p) {
+    using namespace sg3;
+    const int rc = check_conv2d(p);
+    if (rc != SG3_OK) return rc;
+    if (p->precision == SG3_CONV_F16X3) return SG3_CONV2D_FORM_F16X3 + plain_f16x3_form(*p);
+    return ((p->k == 3 ? 2 : 0) + (p->stride == 2 ? 1 : 0)) * 3 + plain_tile(*p);
+}
+
+int sg3_conv2d(const sg3_conv2d_params* p, void* stream) {
+    using namespace sg3;
+    const int rc = check_conv2d(p);
+    if (rc != SG3_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (p->precision == SG3_CONV_F16X3) return dispatch_plain_f16x3(*p, st);
     if (p->k == 3) return p->stride == 1 ? dispatch_plain<3, 1>(*p, st) : dispatch_plain<3, 2>(*p, st);
     return p->stride == 1 ? dispatch_plain<1, 1>(*p, st) : dispatch_plain<1, 2>(*p, st);
 }

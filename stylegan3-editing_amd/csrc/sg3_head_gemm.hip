@@ -15,8 +15,11 @@
 //     in L2), keeps DEPTH k steps of loads in flight (the bytes in flight, not the arithmetic, set the rate), and the four partial
 //     sums meet once, in LDS, in a fixed order (results do not depend on timing);
 //   * arithmetic as in the encoder's convolutions (sg3_conv2d.hip: x = hi + lo in fp16, lo*hi + hi*lo + hi*hi on
-//     v_mfma_f32_32x32x16_f16, fp32 accumulation, fp32-equivalent), with the same range guard: an activation beyond the fp16
-//     range raises *flag and the caller repeats its forward on the exact fp32 path.
+//     v_mfma_f32_32x32x16_f16, fp32 accumulation), with the same range guard: an activation beyond the fp16 range raises *flag
+//     and the caller repeats its forward on the exact fp32 path.  Operands split with split2 (tests/split_model.py): relative
+//     2^-21, plus up to ~2^-23 absolute for activations below 2^-3; every weight column is first lifted by a power of two into
+//     [2^14, 2^15) (head_gemm_colscale_kernel), so that its weights keep the relative bound within 2^-17 of the column's
+//     maximum, and the epilogue multiplies the inverse (colScale, exact) into the sum before the bias.
 // The previous level's LeakyReLU is applied to A on the way in (the unfold kernel does the same for the levels it feeds), so the
 // EqualLinear needs no separate activation pass.
 #include "sg3_common.h"
@@ -27,13 +30,25 @@ namespace sg3 {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct HeadGemmParams {
-    const float* a; const v8h* wp; const float* bias; float* c; int* flag;
+    const float* a; const v8h* wp; const float* colScale; const float* bias; float* c; int* flag;
     int G, M, K, N;
     float slope;
 };
 
+// colScale[g][n] = 2^-e, 2^e = pow2_lift(max_k |w[g][k][n]|): one thread per column (adjacent threads, adjacent columns)
 __global__ void __launch_bounds__(256)
-head_gemm_pack_kernel(const float* __restrict__ w, v8h* __restrict__ wp, int G, int K, int N, int* bad) {
+head_gemm_colscale_kernel(const float* __restrict__ w, float* __restrict__ colScale, int G, int K, int N) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long long)G * N) return;
+    const int g = (int)(t / N), n = (int)(t % N);
+    const float* src = w + (size_t)g * K * N + n;
+    float peak = 0.f;
+    for (int k = 0; k < K; k++) peak = fmaxf(peak, fabsf(src[(size_t)k * N]));
+    colScale[t] = 1.f / pow2_lift(peak);
+}
+
+__global__ void __launch_bounds__(256)
+head_gemm_pack_kernel(const float* __restrict__ w, const float* __restrict__ colScale, v8h* __restrict__ wp, int G, int K, int N, int* bad) {
     // one thread per (g, n block, k step, lane): 8 k values of one column -> a hi and a lo fragment entry
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     const int nk = K >> 4, nb = N >> 5;
@@ -44,13 +59,14 @@ head_gemm_pack_kernel(const float* __restrict__ w, v8h* __restrict__ wp, int G, 
     const int b = (int)(r % nb); const int g = (int)(r / nb);
     const int col = b * 32 + (lane & 31), k0 = kk * 16 + (lane >> 5) * 8;
     const float* src = w + ((size_t)g * K + k0) * N + col;
+    const float lift = 1.f / colScale[(size_t)g * N + col];             // exact: a power of two
     v8h hi, lo;
     float peak = 0.f;
 #pragma unroll
     for (int e = 0; e < 8; e += 2) {
         const float v0 = src[(size_t)e * N], v1 = src[(size_t)(e + 1) * N];
-        peak = fmaxf(peak, fmaxf(fabsf(v0), fabsf(v1)));
-        v2h h, l; split2(v0, v1, h, l);
+        peak = fmaxf(peak, fmaxf(fabsf(v0), fabsf(v1)));                 // the range guard sees the weights as given
+        v2h h, l; split2(v0 * lift, v1 * lift, h, l);
         hi[e] = h.x; hi[e + 1] = h.y; lo[e] = l.x; lo[e + 1] = l.y;
     }
     v8h* dst = wp + ((size_t)(g * nb + b) * nk + kk) * 128 + lane;
@@ -145,12 +161,13 @@ head_gemm_kernel(HeadGemmParams p) {
     if (wave == 0) {
         const int col = nb * 32 + row;
         const float b = p.bias ? p.bias[(size_t)g * p.N + col] : 0.f;
+        const float cs = p.colScale[(size_t)g * p.N + col];
 #pragma unroll
         for (int mb = 0; mb < MB; mb++)
 #pragma unroll
             for (int r = 0; r < 16; r++) {
                 const int m = m0 + mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * kb;
-                const float v = ((acc[mb][r] + red[0][mb][r][lane]) + red[1][mb][r][lane]) + red[2][mb][r][lane] + b;
+                const float v = (((acc[mb][r] + red[0][mb][r][lane]) + red[1][mb][r][lane]) + red[2][mb][r][lane]) * cs + b;
                 if (m < p.M) p.c[((size_t)g * p.M + m) * p.N + col] = v;
             }
     }
@@ -171,27 +188,31 @@ extern "C" long long sg3_head_gemm_packed_halfs(int G, int K, int N) {
     return (long long)G * K * N * 2;
 }
 
-extern "C" int sg3_head_gemm_pack(const float* w, void* packed, int G, int K, int N, int* rangeFlag, void* stream) {
+extern "C" int sg3_head_gemm_pack(const float* w, void* packed, float* colScale, int G, int K, int N, int* rangeFlag, void* stream) {
     using namespace sg3;
-    SG3_REQUIRE(w && packed && rangeFlag, "head_gemm_pack: null tensor");
+    SG3_REQUIRE(w && packed && colScale && rangeFlag, "head_gemm_pack: null tensor");
     SG3_REQUIRE(G > 0 && K > 0 && N > 0 && !(K & 15) && !(N & 31), "head_gemm_pack: K must be a multiple of 16 and N of 32");
     const long long threads = (long long)G * (N >> 5) * (K >> 4) * 64;
     SG3_REQUIRE(threads < (1ll << 39), "head_gemm_pack: too large");
+    const long long cols = (long long)G * N;
+    hipLaunchKernelGGL(head_gemm_colscale_kernel, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       w, colScale, G, K, N);
+    SG3_LAUNCH_CHECK("head_gemm_colscale_kernel");
     hipLaunchKernelGGL(head_gemm_pack_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       w, (v8h*)packed, G, K, N, rangeFlag);
+                       w, (const float*)colScale, (v8h*)packed, G, K, N, rangeFlag);
     SG3_LAUNCH_CHECK("head_gemm_pack_kernel");
     return SG3_OK;
 }
 
 extern "C" int sg3_head_gemm(const sg3_head_gemm_params* q, void* stream) {
     using namespace sg3;
-    SG3_REQUIRE(q && q->a && q->wPacked && q->c && q->rangeFlag, "head_gemm: null tensor");
+    SG3_REQUIRE(q && q->a && q->wPacked && q->colScale && q->c && q->rangeFlag, "head_gemm: null tensor");
     SG3_REQUIRE(q->G > 0 && q->M > 0 && q->K > 0 && q->N > 0, "head_gemm: empty operand");
     SG3_REQUIRE(!(q->K & 15) && !(q->N & 31), "head_gemm: K must be a multiple of 16 and N of 32");
     SG3_REQUIRE((long long)q->M * q->K * 4 < (1ll << 31), "head_gemm: one head's A matrix must stay below 2 GB");
     SG3_REQUIRE(q->G < 65536 && ceil_div(q->M, 32) < 65536, "head_gemm: grid too large");
     HeadGemmParams p;
-    p.a = q->a; p.wp = (const v8h*)q->wPacked; p.bias = q->bias; p.c = q->c; p.flag = q->rangeFlag;
+    p.a = q->a; p.wp = (const v8h*)q->wPacked; p.colScale = q->colScale; p.bias = q->bias; p.c = q->c; p.flag = q->rangeFlag;
     p.G = q->G; p.M = q->M; p.K = q->K; p.N = q->N; p.slope = q->slope;
     hipStream_t st = (hipStream_t)stream;
     if (p.M <= 32) return launch_head_gemm<1, 6>(p, st);

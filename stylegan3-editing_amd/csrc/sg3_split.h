@@ -68,5 +68,14 @@ __device__ __forceinline__ void split2(float x0, float x1, v2h& hi, v2h& lo) {
     hi = __builtin_bit_cast(v2h, __builtin_amdgcn_cvt_pkrtz(h0, h1));
     lo = __builtin_bit_cast(v2h, __builtin_amdgcn_cvt_pkrtz(x0 - h0, x1 - h1));
 }
+// The power of two 2^e (e >= 0) that lifts a weight block's largest |w| into [2^14, 2^15), where both fp16 halves of every
+// weight within 2^-17 of that maximum are normal numbers (a lo below 2^-14 sits on fp16's absolute 2^-24 grid).  Scale up only:
+// a peak of 2^14 or more (and 0, inf, NaN) gives 1.  e <= 126, so 2^e and 2^-e are exact fp32 numbers.
+__device__ __forceinline__ float pow2_lift(float peak) {
+    if (!(peak > 0.f) || !(peak < 16384.f)) return 1.f;
+    int ex;
+    (void)frexpf(peak, &ex);                                   // peak in [2^(ex-1), 2^ex)
+    return ldexpf(1.f, min(15 - ex, 126));
+}
 
 } // namespace sg3

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get('SG3_LIB') or os.path.join(_PKG_ROOT, 'lib', 'libsg3hi
 SG3_OK, SG3_NO_KERNEL, SG3_BAD_ARG, SG3_HIP_ERROR = 0, -1, -2, -3
 SG3_F32, SG3_F16, SG3_F64 = 0, 1, 2
 SG3_CONV_FP32, SG3_CONV_F16X3, SG3_CONV_F16, SG3_CONV_F16X3_F23, SG3_CONV_F16_F23 = 0, 1, 2, 3, 4
+SG3_CONV2D_FORM_F16X3 = 16          # sg3_conv2d_form: first f16x3 form (include/sg3_ops.h)
 _DTYPE = {torch.float32: SG3_F32, torch.float16: SG3_F16, torch.float64: SG3_F64}
 
 c_i32, c_i64, c_f32, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
@@ -84,7 +85,7 @@ class UnfoldParams(ctypes.Structure):
 
 
 class HeadGemmParams(ctypes.Structure):
-    _fields_ = [('a', c_vp), ('wPacked', c_vp), ('bias', c_vp), ('c', c_vp), ('rangeFlag', c_vp),
+    _fields_ = [('a', c_vp), ('wPacked', c_vp), ('colScale', c_vp), ('bias', c_vp), ('c', c_vp), ('rangeFlag', c_vp),
                 ('G', c_i32), ('M', c_i32), ('K', c_i32), ('N', c_i32), ('slope', c_f32)]
 
 
@@ -109,7 +110,7 @@ class WgradParams(ctypes.Structure):
 class Conv2dParams(ctypes.Structure):
     _fields_ = [('x', c_vp), ('wPacked', c_vp), ('inScale', c_vp), ('inShift', c_vp), ('bias', c_vp), ('slope', c_vp), ('out', c_vp),
                 ('N', c_i32), ('I', c_i32), ('O', c_i32), ('H', c_i32), ('W', c_i32), ('k', c_i32), ('stride', c_i32), ('pad', c_i32),
-                ('act', c_i32), ('precision', c_i32), ('rangeFlag', c_vp)]
+                ('act', c_i32), ('precision', c_i32), ('rangeFlag', c_vp), ('wScale', c_vp)]
 
 
 class ImageFinishParams(ctypes.Structure):
@@ -145,16 +146,17 @@ EXPORTS = [
     ('sg3_se_residual', ctypes.c_int, [ctypes.POINTER(SeParams), c_vp]),
     ('sg3_unfold3x3s2', ctypes.c_int, [ctypes.POINTER(UnfoldParams), c_vp]),
     ('sg3_head_gemm_packed_halfs', ctypes.c_int64, [ctypes.c_int] * 3),
-    ('sg3_head_gemm_pack', ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
+    ('sg3_head_gemm_pack', ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
     ('sg3_head_gemm', ctypes.c_int, [ctypes.POINTER(HeadGemmParams), c_vp]),
     ('sg3_modulation_backward', ctypes.c_int, [ctypes.POINTER(ModgradParams), c_vp]),
     ('sg3_modconv_transpose_weights', ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp]),
     ('sg3_modulated_conv2d_prep', ctypes.c_int, [ctypes.POINTER(ModconvPrepParams), c_vp]),
     ('sg3_modulated_conv2d_prep_batch', ctypes.c_int, [ctypes.POINTER(ModconvPrepParams), ctypes.c_int, c_vp]),
     ('sg3_conv2d', ctypes.c_int, [ctypes.POINTER(Conv2dParams), c_vp]),
+    ('sg3_conv2d_form', ctypes.c_int, [ctypes.POINTER(Conv2dParams)]),
     ('sg3_conv2d_wgrad_splits', ctypes.c_int, [ctypes.c_int] * 7 + [ctypes.POINTER(ctypes.c_int)] * 2),
     ('sg3_conv2d_wgrad', ctypes.c_int, [ctypes.POINTER(WgradParams), c_vp]),
-    ('sg3_conv2d_pack', ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp]),
+    ('sg3_conv2d_pack', ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp]),
     ('sg3_resample_coeffs', ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, c_vp, c_vp]),
     ('sg3_image_finish', ctypes.c_int, [ctypes.POINTER(ImageFinishParams), c_vp]),
 ]

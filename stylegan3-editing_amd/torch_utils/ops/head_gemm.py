@@ -4,8 +4,10 @@
 
 For GPU inference this replaces the per-head Conv2d(3x3, stride 2, padding 1) of levels 2.. (as a GEMM over the patch matrix of
 `unfold3x3s2`) and the closing EqualLinear (reference models/setgan/encoder/encoders/map2style.py:8-25).  Split-precision fp16 x 3
-arithmetic, fp32-equivalent; operands outside the fp16 range raise plain_conv's range flag, on which the encoder repeats its forward
-in 'fp32' (torch.baddbmm there: this module has no exact form of its own)."""
+arithmetic: operands relative 2^-21, activations below 2^-3 with up to ~2^-23 absolute error besides, weights lifted per column by
+a power of two (`col_scale` holds the inverse, applied exactly after the sum) so that they keep the relative bound within 2^-17 of
+their column's maximum (tests/split_model.py).  Operands outside the fp16 range raise plain_conv's range flag, on which the encoder
+repeats its forward in 'fp32' (torch.baddbmm there: this module has no exact form of its own)."""
 import ctypes
 
 import torch
@@ -33,11 +35,12 @@ class PackedHeadWeights:
             raise RuntimeError(f'PackedHeadWeights: unsupported shape K={k} (multiple of 16), N={n} (multiple of 32)')
         self.G, self.K, self.N = g, k, n
         self.packed = torch.empty([halfs], dtype=torch.float16, device=w.device)
+        self.col_scale = torch.empty([g, n], dtype=torch.float32, device=w.device)
         self.bias = None if bias is None else bias.reshape(g, n).to(torch.float32).contiguous()
         flag = torch.zeros([1], dtype=torch.int32, device=w.device)
         w = w.contiguous()
         with torch.cuda.device(w.device):
-            abi.check(lib.sg3_head_gemm_pack(abi.ptr(w), abi.ptr(self.packed), g, k, n, abi.ptr(flag), abi.stream_ptr(w.device)),
+            abi.check(lib.sg3_head_gemm_pack(abi.ptr(w), abi.ptr(self.packed), abi.ptr(self.col_scale), g, k, n, abi.ptr(flag), abi.stream_ptr(w.device)),
                       'sg3_head_gemm_pack')
         self.usable = int(flag.item()) == 0
 
@@ -51,7 +54,8 @@ class PackedHeadWeights:
         m = int(a.shape[1])
         out = torch.empty([self.G, m, self.N], dtype=torch.float32, device=a.device)
         p = abi.HeadGemmParams()
-        p.a, p.wPacked, p.bias, p.c = abi.ptr(a), abi.ptr(self.packed), (abi.ptr(self.bias) if self.bias is not None else None), abi.ptr(out)
+        p.a, p.wPacked, p.colScale, p.c = abi.ptr(a), abi.ptr(self.packed), abi.ptr(self.col_scale), abi.ptr(out)
+        p.bias = abi.ptr(self.bias) if self.bias is not None else None
         p.rangeFlag = abi.ptr(plain_conv._flag(a.device))
         p.G, p.M, p.K, p.N, p.slope = self.G, m, self.K, self.N, float(slope)
         with torch.cuda.device(a.device):

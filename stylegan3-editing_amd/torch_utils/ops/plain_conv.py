@@ -16,9 +16,11 @@ ACT_NONE, ACT_PRELU, ACT_LRELU = 0, 1, 2
 
 # Arithmetic of the convolutions (3x3 stride 1: the bulk of the backbone; 3x3 stride 2: the first unit of each stage and level 1
 # of the style heads; 1x1: the projection shortcuts):
-#   'f16x3' : fp16 hi/lo operand split, three fp16 MFMAs per K step, fp32 accumulation (fp32-equivalent, 5.3x the fp32 MFMA
-#             rate).  Operands must stay inside the fp16 range; every launch checks that on the device and raises a flag
-#             (`overflowed`), on which the caller repeats its forward with 'fp32'.
+#   'f16x3' : fp16 hi/lo operand split, three fp16 MFMAs per K step, fp32 accumulation (5.3x the fp32 MFMA rate).  Per operand:
+#             activations relative 2^-21 plus up to ~2^-23 absolute (below |x| = 2^-3 the halves leave fp16's normal range);
+#             weights lifted per output channel by a power of two when packed (undone exactly in the epilogue), relative 2^-22
+#             within 2^-17 of their channel's maximum (tests/split_model.py).  Operands must stay inside the fp16 range; every
+#             launch checks that on the device and raises a flag (`overflowed`), on which the caller repeats its forward with 'fp32'.
 #   'fp32'  : v_mfma_f32_32x32x2_f32, exact products.
 precision = 'f16x3'
 _flags = {}
@@ -54,6 +56,7 @@ class PackedConv:
         f32 = lambda t: None if t is None else t.detach().to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
         self.out_scale, self.bias, self.in_scale, self.in_shift, self.slope = f32(out_scale), f32(bias), f32(in_scale), f32(in_shift), f32(slope)
         self._packed = {}
+        self._scales = {}
 
     def packed(self, prec):
         """Packed operand image for one arithmetic form (built on first use)."""
@@ -61,13 +64,39 @@ class PackedConv:
             lib = abi.load()
             dev = self._w.device
             buf = torch.empty([int(lib.sg3_modconv_packed_floats(self.O, self.I, self.k, prec))], dtype=torch.float32, device=dev)
+            scale = torch.empty([self.O], dtype=torch.float32, device=dev) if prec == abi.SG3_CONV_F16X3 else None
             with torch.cuda.device(dev):
-                abi.check(lib.sg3_conv2d_pack(abi.ptr(self._w), abi.ptr(self.out_scale), abi.ptr(buf), self.O, self.I, self.k, prec, abi.stream_ptr(dev)), 'sg3_conv2d_pack')
-            self._packed[prec] = buf
+                abi.check(lib.sg3_conv2d_pack(abi.ptr(self._w), abi.ptr(self.out_scale), abi.ptr(buf), abi.ptr(scale), self.O, self.I, self.k, prec,
+                                              abi.stream_ptr(dev)), 'sg3_conv2d_pack')
+            self._packed[prec], self._scales[prec] = buf, scale
         return self._packed[prec]
+
+    def weight_scale(self, prec):
+        """[O] inverse powers of two the f16x3 pack lifted the output channels by (None for 'fp32')."""
+        self.packed(prec)
+        return self._scales[prec]
 
     def __call__(self, x):
         return self.run(x)
+
+    def _params(self, x, out):
+        split = precision == 'f16x3'
+        prec = abi.SG3_CONV_F16X3 if split else abi.SG3_CONV_FP32
+        n, _, h, w = (int(v) for v in x.shape)
+        p = abi.Conv2dParams()
+        p.x, p.wPacked, p.out = abi.ptr(x), abi.ptr(self.packed(prec)), abi.ptr(out)
+        p.precision, p.rangeFlag, p.wScale = prec, (abi.ptr(_flag(x.device)) if split else None), abi.ptr(self._scales[prec])
+        p.inScale, p.inShift, p.bias, p.slope = abi.ptr(self.in_scale), abi.ptr(self.in_shift), abi.ptr(self.bias), abi.ptr(self.slope)
+        p.N, p.I, p.O, p.H, p.W = n, self.I, self.O, h, w
+        p.k, p.stride, p.pad, p.act = self.k, self.stride, self.padding, self.act
+        return p
+
+    def form(self, x):
+        """The kernel form `run(x)` launches under the current `precision` (sg3_conv2d_form: 0 .. 11 for 'fp32',
+        abi.SG3_CONV2D_FORM_F16X3 + 0 .. 5 for 'f16x3'); nothing is launched."""
+        assert x.is_cuda and x.ndim == 4 and x.shape[1] == self.I
+        with torch.cuda.device(x.device):
+            return int(abi.load().sg3_conv2d_form(ctypes.byref(self._params(x, x))))
 
     def run(self, x):
         assert x.is_cuda and x.dtype == torch.float32 and x.ndim == 4 and x.shape[1] == self.I
@@ -76,14 +105,7 @@ class PackedConv:
         oh = (h + 2 * self.padding - self.k) // self.stride + 1
         ow = (w + 2 * self.padding - self.k) // self.stride + 1
         out = torch.empty([n, self.O, oh, ow], dtype=torch.float32, device=x.device)
-        split = precision == 'f16x3'
-        prec = abi.SG3_CONV_F16X3 if split else abi.SG3_CONV_FP32
-        p = abi.Conv2dParams()
-        p.x, p.wPacked, p.out = abi.ptr(x), abi.ptr(self.packed(prec)), abi.ptr(out)
-        p.precision, p.rangeFlag = prec, (abi.ptr(_flag(x.device)) if split else None)
-        p.inScale, p.inShift, p.bias, p.slope = abi.ptr(self.in_scale), abi.ptr(self.in_shift), abi.ptr(self.bias), abi.ptr(self.slope)
-        p.N, p.I, p.O, p.H, p.W = n, self.I, self.O, h, w
-        p.k, p.stride, p.pad, p.act = self.k, self.stride, self.padding, self.act
+        p = self._params(x, out)
         with torch.cuda.device(x.device):
             abi.check(abi.load().sg3_conv2d(ctypes.byref(p), abi.stream_ptr(x.device)), 'sg3_conv2d')
         return out
