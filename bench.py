@@ -12,7 +12,14 @@ One JSON line is printed by rank 0:
   metric/value : whole-job images per second
   roofline     : filtered_lrelu streaming kernel -- algorithmic bytes (C*(in^2+out^2)*4 per image and layer,
                  SURVEY 8d) / its summed launch time measured with HIP events on the launch stream, vs 8 TB/s
+  modconv      : the modulated convolutions' FLOP rate over their launch time, vs the dense fp16 MFMA peak
+  inversion, inversion_T1024, extras : ReStyle inversion, mixed precision, config R, PTI steps (secondary workloads)
   cpu_baseline : the CPU oracle (C/OpenMP port of the reference ref path) timed on this host for ONE image
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line, in which roofline, modconv, inversion,
+inversion_T1024, extras and cpu_baseline are null.  --full measures them too: roofline and modconv from an eager pass after the timed
+graph replays, then the secondary workloads and the CPU oracle (--no-inversion / --no-extras / --no-cpu-baseline leave one out).  An
+--eager run brackets the launches of its timed steps with events, so it reports roofline and modconv without --full as well.
 
 --dump-outputs DIR writes the images of the last timed step (rank 0) to DIR as .npy files: inputs and weights are seeded, so
 two builds run with the same arguments can be compared output for output.
@@ -443,10 +450,12 @@ def main(argv=None):
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--batch', type=int, default=8, help='images per GPU per step')
     ap.add_argument('--config', default='T1024')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-inversion', action='store_true', help='skip the secondary ReStyle inversion measurement')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also measure the per-kernel roofline figures, the secondary workloads and the CPU baseline')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU oracle baseline')
+    ap.add_argument('--no-inversion', action='store_true', help='with --full: skip the secondary ReStyle inversion measurement')
     ap.add_argument('--eager', action='store_true', help='launch kernel by kernel instead of replaying a captured hipGraph')
-    ap.add_argument('--no-extras', action='store_true', help='skip the secondary mixed-precision / config-R measurements')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the secondary mixed-precision / config-R measurements')
     ap.add_argument('--dry-run', action='store_true', help='CPU rehearsal of the launch path (gloo, stub step); prints a line with value null')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help="after the timed steps, write rank 0's images of the last timed step to DIR as .npy (see dump_outputs)")
@@ -490,7 +499,7 @@ def main(argv=None):
     graphed = None
     if not args.eager:
         # the timed job replays ONE captured hipGraph per step; per-kernel HIP-event timing for the roofline line is
-        # taken from an eager pass after the timed region (events cannot be recorded inside a graph replay)
+        # taken (--full) from an eager pass after the timed region (events cannot be recorded inside a graph replay)
         from sg3_runtime import GraphedSynthesis
         eager_step = step
         try:
@@ -524,21 +533,21 @@ def main(argv=None):
     timer.enabled = False
     if args.dump_outputs and rank == 0:
         dump_outputs(img, args.dump_outputs)         # before anything else runs: the graph's output buffer is reused by a replay
-    ksteps = args.steps
-    if graphed is not None:
+    kernel_figures = args.full or args.eager          # an eager run's timed steps bracketed their own launches with events
+    if args.full and graphed is not None:
         # same kernels, same inputs, launched eagerly so each launch can be bracketed by events on its stream
-        ksteps = max(3, min(args.steps, 10))
         timer.enabled = True
-        for _ in range(ksteps):
+        for _ in range(max(3, min(args.steps, 10))):
             eager_step()
         torch.cuda.synchronize()
         timer.enabled = False
     assert tuple(img.shape) == (args.batch, 3, G.img_resolution, G.img_resolution) and bool(torch.isfinite(img).all())
-    # per step: the 14 streaming filtered_lrelu launches; 16 convolution launches (the channel mix of the Fourier-feature input runs on
-    # the 1x1 kernel too).  Read here: the inversion / PTI legs below reuse (and reset) the timer for their own roofline objects
-    total_bytes, fl_layers = flrelu_algorithmic_bytes(G, args.batch)
-    fl_ms = timer.median_step_ms('filtered_lrelu', len(fl_layers))
-    conv_ms = timer.median_step_ms('modulated_conv2d', len(G.synthesis.layer_names) + 1)
+    if kernel_figures:
+        # per step: the 14 streaming filtered_lrelu launches; 16 convolution launches (the channel mix of the Fourier-feature input runs
+        # on the 1x1 kernel too).  Read here: the inversion / PTI legs below reuse (and reset) the timer for their own roofline objects
+        total_bytes, fl_layers = flrelu_algorithmic_bytes(G, args.batch)
+        fl_ms = timer.median_step_ms('filtered_lrelu', len(fl_layers))
+        conv_ms = timer.median_step_ms('modulated_conv2d', len(G.synthesis.layer_names) + 1)
     timer.reset()
 
     t = torch.tensor([dt], dtype=torch.float64, device=device)
@@ -547,7 +556,7 @@ def main(argv=None):
     dt = float(t.item())
 
     inversion = inversion_t = None
-    if not args.no_inversion and args.config == 'T1024':
+    if args.full and not args.no_inversion and args.config == 'T1024':
         # the reference's default decoder is config R (models/stylegan3/model.py:42-54); the config-T
         # decoder of the headline workload is measured beside it
         G_r = build_generator('R1024', device)
@@ -556,26 +565,40 @@ def main(argv=None):
         torch.cuda.empty_cache()
         inversion_t = bench_inversion(G, device, rank, world, decoder='T-1024', timer=None)
     extras = None
-    if not args.no_extras and world == 1 and args.config == 'T1024':
+    if args.full and not args.no_extras and world == 1 and args.config == 'T1024':
         extras = bench_extras(G, ws, device, timer=timer)
 
     if rank == 0:
-        achieved = total_bytes / (fl_ms * 1e-3) / 1e9 if fl_ms > 0 else 0.0
-        # HBM traffic of the same 14 launches from PMC counters (FETCH_SIZE x2 + WRITE_SIZE, separate rocprofv3 passes over this
-        # command, summarised by tools/sum_traffic.py, which stamps the kernel source it ran on); only valid for the default workload
-        # and for THIS kernel source -- a stale file reads as null
-        traffic = None
-        tfile = os.path.join(ROOT, 'profiles', 'flrelu_traffic.json')
-        if os.path.exists(tfile) and args.batch == 8 and args.config == 'T1024':
-            with open(tfile) as f:
-                tj = json.load(f)
-            if tj.get('kernel_source_sha') == kernel_source_sha():
-                traffic = tj['traffic_bytes_per_step']
-        rows = conv_flop_table(G, args.batch)
-        conv_flop = sum(f for f, _ in rows)
-        conv_issued = sum(f * k for f, k in rows)
-        conv_tflops = conv_flop / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
-        issued_tflops = conv_issued / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
+        roofline = modconv = None
+        if kernel_figures:
+            achieved = total_bytes / (fl_ms * 1e-3) / 1e9 if fl_ms > 0 else 0.0
+            # HBM traffic of the same 14 launches from PMC counters (FETCH_SIZE x2 + WRITE_SIZE, separate rocprofv3 passes over this
+            # command, summarised by tools/sum_traffic.py, which stamps the kernel source it ran on); only valid for the default
+            # workload and for THIS kernel source -- a stale file reads as null
+            traffic = None
+            tfile = os.path.join(ROOT, 'profiles', 'flrelu_traffic.json')
+            if os.path.exists(tfile) and args.batch == 8 and args.config == 'T1024':
+                with open(tfile) as f:
+                    tj = json.load(f)
+                if tj.get('kernel_source_sha') == kernel_source_sha():
+                    traffic = tj['traffic_bytes_per_step']
+            rows = conv_flop_table(G, args.batch)
+            conv_flop = sum(f for f, _ in rows)
+            conv_issued = sum(f * k for f, k in rows)
+            conv_tflops = conv_flop / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
+            issued_tflops = conv_issued / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
+            roofline = {'bound': 'hbm', 'kernel': 'flrelu_stream_kernel', 'achieved': achieved, 'peak': HBM_PEAK_GBS,
+                        'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS, 'traffic': traffic,
+                        'algorithmic_bytes_per_step': total_bytes, 'kernel_ms_per_step': fl_ms}
+            # second roofline, same shape: the modulated convolutions against the dense fp16 MFMA peak.  `achieved` / `frac` are the
+            # ALGORITHMIC fp32 FLOP rate (2 I O k^2 out^2 per image and layer); `issued` / `issued_frac` count the fp16 matrix-core
+            # work issued for it: three products per fp32 product in the split-precision kernels, two where the transform-domain 3x3
+            # kernel (Winograd F(2,3) along x: two thirds of the contractions) runs
+            modconv = {'bound': 'mfma', 'kernel': 'modconv_f23_kernel / modconv_f16x3_kernel (+input mix, ToRGB 1x1)', 'achieved': conv_tflops,
+                       'peak': MFMA_F16_PEAK_TFLOPS, 'unit': 'TFLOP/s', 'frac': conv_tflops / MFMA_F16_PEAK_TFLOPS,
+                       'issued': issued_tflops, 'issued_frac': issued_tflops / MFMA_F16_PEAK_TFLOPS,
+                       'algorithmic_flop_per_step': conv_flop, 'kernel_ms_per_step': conv_ms,
+                       'f23_layers': sum(1 for _, k in rows if k == 2.0)}
         out = {
             'metric': 'FFHQ-1024 StyleGAN3-T synthesis imgs/sec', 'value': args.batch * world * args.steps / dt, 'unit': 'imgs/s',
             'n_gpus': world, 'world_size_observed': dist.get_world_size() if world > 1 else 1, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': dt / args.steps * 1e3,
@@ -583,23 +606,13 @@ def main(argv=None):
             'config': {'workload': f'StyleGAN3-T FFHQ-1024 Generator.synthesis forward, batch {args.batch} per GPU, force_fp32 '
                                    f'(BASELINE configs[1]); seeded random weights', 'per_gpu_batch': args.batch, 'sharding': 'images',
                        'launch': 'eager' if args.eager else 'hipGraph replay'},
-            'roofline': {'bound': 'hbm', 'kernel': 'flrelu_stream_kernel', 'achieved': achieved, 'peak': HBM_PEAK_GBS,
-                         'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS, 'traffic': traffic,
-                         'algorithmic_bytes_per_step': total_bytes, 'kernel_ms_per_step': fl_ms},
-            # second roofline, same shape: the modulated convolutions against the dense fp16 MFMA peak.  `achieved` / `frac` are the
-            # ALGORITHMIC fp32 FLOP rate (2 I O k^2 out^2 per image and layer); `issued` / `issued_frac` count the fp16 matrix-core work
-            # issued for it: three products per fp32 product in the split-precision kernels, two where the transform-domain 3x3 kernel
-            # (Winograd F(2,3) along x: two thirds of the contractions) runs
-            'modconv': {'bound': 'mfma', 'kernel': 'modconv_f23_kernel / modconv_f16x3_kernel (+input mix, ToRGB 1x1)', 'achieved': conv_tflops,
-                        'peak': MFMA_F16_PEAK_TFLOPS, 'unit': 'TFLOP/s', 'frac': conv_tflops / MFMA_F16_PEAK_TFLOPS,
-                        'issued': issued_tflops, 'issued_frac': issued_tflops / MFMA_F16_PEAK_TFLOPS,
-                        'algorithmic_flop_per_step': conv_flop, 'kernel_ms_per_step': conv_ms,
-                        'f23_layers': sum(1 for _, k in rows if k == 2.0)},
+            'roofline': roofline,
+            'modconv': modconv,
         }
         out['inversion'] = inversion
         out['inversion_T1024'] = inversion_t
         out['extras'] = extras
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out['cpu_baseline'] = cpu_baseline(args.config)
         else:
             out['cpu_baseline'] = None

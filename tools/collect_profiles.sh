@@ -9,7 +9,7 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp PYTHONUNBUFFERED=1
-SHORT="--no-inversion --no-extras --no-cpu-baseline"
+SHORT="--full --no-inversion --no-extras --no-cpu-baseline"
 EAGER="--eager --steps 2 --warmup 1 $SHORT"
 
 echo "[1/6] kernel trace + stats of the default bench (short form)"
@@ -37,7 +37,7 @@ rm -rf "$OUT/traceR"
 
 echo "[5/6] the full bench line (traffic figure of step 2 in place)"
 cp "$OUT/flrelu_traffic.json" profiles/flrelu_traffic.json
-python3 bench.py > "$OUT/bench_line.json" 2> "$OUT/bench.err"
+python3 bench.py --full > "$OUT/bench_line.json" 2> "$OUT/bench.err"
 
 echo "[6/6] done"
 ls -la "$OUT"
