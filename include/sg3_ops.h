@@ -627,6 +627,36 @@ typedef struct sg3_image_finish_params {
 SG3_API int sg3_resample_coeffs(int32_t inSize, int32_t outSize, int32_t* bounds, int32_t* coeffs);
 SG3_API int sg3_image_finish(const sg3_image_finish_params* p, void* stream);
 
+/* ----------------------------------------------------------------------
+ * StyleCLIP latent mapper forward (reference editing/styleclip_mapper/latent_mappers.py: Mapper = PixelNorm over dim 1 -- the
+ * levels of one sample -- then 4 x EqualLinear(512, 512, lr_mul=0.01, activation='fused_lrelu'); LevelsMapper runs one Mapper per
+ * level group, a disabled group gives zeros; scripts/inference.py: w_hat = w + 0.1 * mapper(w)).  For every group g and every
+ * sample n, on the levels l of [levelBegin[g], levelEnd[g]):
+ *     h0 = x[n,l,:] * rsqrt(mean over the group's levels of x[n,l,:]^2 + 1e-8)
+ *     h(i+1) = leaky_relu(h(i) @ weight[g][i]^T + bias[g][i], 0.2) * sqrt(2)        i = 0..3
+ *     delta[n,l,:] = h4,   out[n,l,:] = x[n,l,:] + alpha * delta[n,l,:]
+ *   and on levels in no group delta = 0, out = x + alpha * 0.  weight [groups][4][512][512] is the prepared (W * scale) in the
+ *   stored [out][in] order, bias [groups][4][512] is b * lr_mul; float32 throughout, fp32 products and fp32 accumulation in a fixed
+ *   order, so a sample's result does not depend on the batch it is in.  x, out, delta are dense [N][L][D]; out or delta may be
+ *   NULL (not both).  scratch: 2 * N * L * D floats (may be NULL when groups == 0).  weight and scratch 16-byte aligned; the written
+ *   buffers overlap no other.  D must be 512, L at most 32, groups 0..4, groups non-empty and disjoint.  Five launches (one when groups == 0).
+ * ---------------------------------------------------------------------- */
+typedef struct sg3_latent_mapper_params {
+    const float*   x;              /* [N][L][D] */
+    const float*   weight;         /* [groups][4][D][D] */
+    const float*   bias;           /* [groups][4][D] */
+    float*         out;            /* [N][L][D] or NULL */
+    float*         delta;          /* [N][L][D] or NULL */
+    float*         scratch;        /* 2 * N * L * D floats */
+    int32_t        N, L, D;
+    int32_t        groups;
+    int32_t        levelBegin[4];
+    int32_t        levelEnd[4];
+    float          alpha;
+} sg3_latent_mapper_params;
+
+SG3_API int sg3_latent_mapper(const sg3_latent_mapper_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

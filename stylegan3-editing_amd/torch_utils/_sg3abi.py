@@ -119,6 +119,12 @@ class ImageFinishParams(ctypes.Structure):
                 ('boundsH', c_vp), ('coeffsH', c_vp), ('kH', c_i32), ('boundsV', c_vp), ('coeffsV', c_vp), ('kV', c_i32)]
 
 
+class LatentMapperParams(ctypes.Structure):
+    _fields_ = [('x', c_vp), ('weight', c_vp), ('bias', c_vp), ('out', c_vp), ('delta', c_vp), ('scratch', c_vp),
+                ('N', c_i32), ('L', c_i32), ('D', c_i32), ('groups', c_i32), ('levelBegin', c_i32 * 4), ('levelEnd', c_i32 * 4),
+                ('alpha', c_f32)]
+
+
 # every symbol include/sg3_ops.h declares: (name, restype, argtypes)
 EXPORTS = [
     ('sg3_abi_version', ctypes.c_int, []),
@@ -159,6 +165,7 @@ EXPORTS = [
     ('sg3_conv2d_pack', ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp]),
     ('sg3_resample_coeffs', ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, c_vp, c_vp]),
     ('sg3_image_finish', ctypes.c_int, [ctypes.POINTER(ImageFinishParams), c_vp]),
+    ('sg3_latent_mapper', ctypes.c_int, [ctypes.POINTER(LatentMapperParams), c_vp]),
 ]
 
 _lib = None
