@@ -299,13 +299,25 @@ def _bound_scalar(value, device):
 def _weight_gradient(x, dy, k, padding, x_amax=None, dy_amax=None):
     """dW[n,o,i,ky,kx] = sum_pixels dy[n,o] * x[n,i] (shifted): the per-sample weight gradient on the matrix cores
     (csrc/sg3_wgrad.hip).  The pixel dimension is split over workgroups; the partial sums are added here."""
+    n, co, ci = int(x.shape[0]), int(dy.shape[1]), int(x.shape[1])
+    partial = _weight_gradient_partials(x, dy, k, padding, x_amax, dy_amax)
+    return partial.sum(dim=0).permute(0, 2, 3, 1).reshape(n, co, ci, k, k)
+
+
+def _weight_gradient_partials(x, dy, k, padding, x_amax=None, dy_amax=None, partial=None):
+    """The weight-gradient launch of `_weight_gradient`: returns its per-split partial sums [nBands * nSegGroups, N, k*k, O, I]
+    (split = band * nSegGroups + segment group, see sg3_conv2d_wgrad_splits), written into `partial` if given."""
     lib = abi.load()
     x = x.contiguous(); dy = dy.contiguous()
     n, ci, h, w = (int(v) for v in x.shape)
     co = int(dy.shape[1])
     nb, ng = ctypes.c_int(), ctypes.c_int()
     abi.check(lib.sg3_conv2d_wgrad_splits(n, ci, co, h, w, k, int(padding), ctypes.byref(nb), ctypes.byref(ng)), 'sg3_conv2d_wgrad_splits')
-    partial = torch.empty([nb.value * ng.value, n, k * k, co, ci], dtype=torch.float32, device=x.device)
+    shape = [nb.value * ng.value, n, k * k, co, ci]
+    if partial is None:
+        partial = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif list(partial.shape) != shape or partial.dtype != torch.float32 or not partial.is_contiguous():
+        raise RuntimeError(f'_weight_gradient_partials: partial must be a contiguous float32 {shape} tensor')
     sx = x_amax if x_amax is not None else _amax(x)            # the kernel derives the power-of-two scales from the maxima
     sd = dy_amax if dy_amax is not None else _amax(dy)
     sx, sd = sx.to(torch.float32).reshape(1), sd.to(torch.float32).reshape(1)
@@ -317,7 +329,7 @@ def _weight_gradient(x, dy, k, padding, x_amax=None, dy_amax=None):
     p.nBands, p.nSegGroups = nb.value, ng.value
     with torch.cuda.device(x.device):
         abi.check(lib.sg3_conv2d_wgrad(ctypes.byref(p), abi.stream_ptr(x.device)), 'sg3_conv2d_wgrad')
-    return partial.sum(dim=0).permute(0, 2, 3, 1).reshape(n, co, ci, k, k)
+    return partial
 
 
 # First-order gradients of w and s go through the closed-form kernels of csrc/sg3_modgrad.hip unless SG3_MODGRAD_AUTOGRAD=1
