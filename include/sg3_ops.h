@@ -129,6 +129,14 @@ SG3_API int sg3_filtered_lrelu_finish_partials(const float* sumPartial, const fl
  * 0 when the call does not take the streaming kernel.  For tests and profiling; no reference counterpart. */
 SG3_API int sg3_filtered_lrelu_planes_per_wave(const sg3_filtered_lrelu_params* p);
 
+/* Host-only query: the work decomposition `sg3_filtered_lrelu` launches for this call, from the functions the launch itself uses.
+ * Output rows are cut into nChunks chunks of chunkRows rows (the last one shorter); output columns into nStrips strips: equal strips
+ * of stripW columns (nFullStrips = 0), or nFullStrips strips of stripW = 120 columns, one plane per wave, followed by one remainder
+ * strip with two planes per wave (planes_per_wave = 3).  ySumPartial / yAbsMaxPartial slot of a workgroup: chunk * nStrips + strip.
+ * Returns 1, or 0 (nothing written) when the call does not take the streaming kernel.  For tests; no reference counterpart. */
+SG3_API int sg3_filtered_lrelu_stream_grid(const sg3_filtered_lrelu_params* p, int* nStrips, int* stripW, int* nFullStrips, int* nChunks,
+                                           int* chunkRows);
+
 /* host-only: the bound on |input + bias| under which the plain forward's streaming kernel evaluates lrelu + clamp as one
  * med3(u, slope*u, clamp/gain) -- the same computation the kernel makes from the separable up filter fu (fuW taps, HOST
  * memory here).  -1 when there is none (clamp/gain not positive). */

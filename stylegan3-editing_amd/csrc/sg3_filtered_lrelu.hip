@@ -375,7 +375,7 @@ struct Stream {
                 liveGain = (wide ? mw : (m & first)) != 0ull ? __builtin_bit_cast(float, 0x7fc00000u) : liveGain;
                 liveGain1 = (wide ? mw : (m & ~first)) != 0ull ? __builtin_bit_cast(float, 0x7fc00000u) : liveGain1;
             }
-        } else if (SIGNS == 0 && SG3_NAN_GUARD) {
+        } else if (SIGNS <= 1 && SG3_NAN_GUARD) {           // the sign-writing forward too: its outputs are the plain forward's
 #pragma unroll
             for (int q = 0; q < Cfg::NL - 1; q++) {
                 unsigned long long m;            // asm: the file is built with -fno-honor-nans, which folds the NaN classes away
@@ -416,9 +416,9 @@ struct Stream {
         }
         // ---- U new upsampled rows ----
         const float slope = p.slope, clampv = p.clamp / p.gain, gain = p.gain;
-        // sign-write mode applies the gain before the nonlinearity; the 2-D up filter's taps carry no up^2 factor
-        const float gainOut = (SIGNS == 1) ? 1.f : (UP2D ? p.gain * (float)(U * U) :
-                              ((SIGNS == 0 && (SG3_NAN_GUARD || FAST)) ? ((G > 1 && lane >= 32 && !FAST) ? liveGain1 : liveGain) : p.gain));
+        // the 2-D up filter's taps carry no up^2 factor
+        const float gainOut = UP2D ? p.gain * (float)(U * U) :
+                              ((SIGNS <= 1 && (SG3_NAN_GUARD || FAST)) ? ((G > 1 && lane >= 32 && !FAST) ? liveGain1 : liveGain) : p.gain);
 #pragma unroll
         for (int j = 0; j < U; j++) {
             const int kv = U - 1 - j;                          // vertical up phase of this row
@@ -482,9 +482,14 @@ struct Stream {
                     const unsigned code = bits >> (2 * c);
                     a[c] *= (code & 2u) ? 0.f : ((code & 1u) ? slope : 1.f);
                 }
-            } else if (SIGNS == 1) {
-                // training forward: the reference's exact order (gain, lrelu, clamp; filtered_lrelu.cu sign write) so that
-                // the sign codes agree with it: 1 = negative, 2 = clamped
+            }
+            if (SIGNS == 1) {
+                // training forward: the sign codes are decided in the reference's exact order (gain, lrelu, clamp; filtered_lrelu.cu
+                // sign write) so that they agree with it: 1 = negative, 2 = clamped.  The output VALUES are formed below exactly as
+                // the plain forward forms them (gain once per output sample), so that training reproduces inference bit for bit.
+                // The code compares fl(gain * u) with clamp, the value clamps u at fl(clamp / gain): within a rounding of the
+                // threshold a sample can carry the code "clamped" with an unclamped value or the reverse -- a difference of one
+                // rounding of clamp in y, and a sample whose gradient multiplier is within rounding of its jump anyway.
                 unsigned code = 0;
 #pragma unroll
                 for (int c = 0; c < 4; c++) {
@@ -492,7 +497,6 @@ struct Stream {
                     const bool neg = v < 0.f;
                     const float lv = neg ? v * slope : v;
                     const bool big = __builtin_fabsf(lv) > p.clamp;
-                    a[c] = big ? __builtin_copysignf(p.clamp, lv) : lv;
                     code |= (big ? 2u : (neg ? 1u : 0u)) << (2 * c);
                 }
                 const int sr = uy + p.sy;
@@ -505,13 +509,14 @@ struct Stream {
                     const __amdgpu_buffer_rsrc_t ss = __builtin_amdgcn_make_buffer_rsrc((void*)(splane + (long long)sr * p.sWb), (short)0, p.sWb, 0x00020000);
                     __builtin_amdgcn_raw_buffer_store_b8((unsigned char)byte, ss, bofs, 0, 0);
                 }
-            } else if (FAST) {
+            }
+            if (SIGNS != 2 && FAST) {
                 // lrelu + clamp in one instruction: med3(u, slope u, c) = med3(max(u, slope u), -c, c) whenever slope |u| <= c (u < 0:
                 // slope u; 0 <= u <= c: u; u > c: c -- exact selections), which the threshold test on the staged samples guarantees
                 const v2f s0 = u0 * splat(slope), s1 = u1 * splat(slope);
                 a[0] = __builtin_amdgcn_fmed3f(u0.x, s0.x, clampv); a[1] = __builtin_amdgcn_fmed3f(u0.y, s0.y, clampv);
                 a[2] = __builtin_amdgcn_fmed3f(u1.x, s1.x, clampv); a[3] = __builtin_amdgcn_fmed3f(u1.y, s1.y, clampv);
-            } else {
+            } else if (SIGNS != 2) {
                 // leaky ReLU (slope <= 1 so lrelu(v) = max(v, slope*v)) and clamp.  The activation gain g > 0 commutes with
                 // both: clamp_c(lrelu(g*u)) = g * clamp_{c/g}(lrelu(u)), so g is applied once per OUTPUT sample after the
                 // down filter instead of once per upsampled sample (clampv = clamp / gain here)
@@ -1216,6 +1221,21 @@ int sg3_filtered_lrelu_planes_per_wave(const sg3_filtered_lrelu_params* p) {
     if (nStrips == 1) return stream_packs_planes(*p, p->yW) ? 2 : 1;
     const int nFull = stream_full_strips(p->yW, nStrips);
     return (nFull > 0 && stream_packs_planes(*p, p->yW - nFull * STREAM_FULL_TW)) ? 3 : 1;
+}
+
+int sg3_filtered_lrelu_stream_grid(const sg3_filtered_lrelu_params* p, int* nStrips, int* stripW, int* nFullStrips, int* nChunks, int* chunkRows) {
+    using namespace sg3;
+    if (sg3_filtered_lrelu_planes_per_wave(p) == 0) return 0;           // not a streaming-kernel call
+    int ns, tw, nc, ch;
+    stream_grid(p->N, p->C, p->yH, p->yW, p->down, ns, tw, nc, ch);
+    // the cut `launch_stream` makes: full 120-column strips + a two-plane remainder strip where that applies, equal strips otherwise
+    const int nFull = (ns > 1 && stream_packs_planes(*p, p->yW - stream_full_strips(p->yW, ns) * STREAM_FULL_TW)) ? stream_full_strips(p->yW, ns) : 0;
+    if (nStrips) *nStrips = ns;
+    if (stripW) *stripW = nFull > 0 ? STREAM_FULL_TW : tw;
+    if (nFullStrips) *nFullStrips = nFull;
+    if (nChunks) *nChunks = nc;
+    if (chunkRows) *chunkRows = ch;
+    return 1;
 }
 
 int sg3_filtered_lrelu(const sg3_filtered_lrelu_params* p, void* stream) {

@@ -18,6 +18,8 @@ import torch
 from . import _sg3abi as abi
 
 INT_MAX = 2 ** 31 - 1
+stream_call_log = None          # set to a list to record, per filtered_lrelu call, its work decomposition (sg3_filtered_lrelu_stream_grid) and,
+                                # for adjoint calls, the per-workgroup partial sums / maxima (tests)
 planes_per_wave_log = None      # set to a list to record sg3_filtered_lrelu_planes_per_wave of every filtered_lrelu call
 
 
@@ -129,6 +131,12 @@ class FilteredLreluPlugin:
                     p.yAbsMaxPartial = abi.ptr(partial_max)
         if planes_per_wave_log is not None:            # tests: which form of the streaming kernel this call takes (host-only query)
             planes_per_wave_log.append(int(lib.sg3_filtered_lrelu_planes_per_wave(ctypes.byref(p))))
+        if stream_call_log is not None:
+            g = [ctypes.c_int() for _ in range(5)]
+            ok = lib.sg3_filtered_lrelu_stream_grid(ctypes.byref(p), *[ctypes.byref(v) for v in g])
+            stream_call_log.append(dict(read=bool(readSigns), write=bool(writeSigns), shape=(N, C, yH.value, yW.value), up=int(up), down=int(down),
+                                        planes_per_wave=int(lib.sg3_filtered_lrelu_planes_per_wave(ctypes.byref(p))),
+                                        grid=tuple(v.value for v in g) if ok else None, partial=partial, partial_max=partial_max))
         with torch.cuda.device(x.device):
             rc = lib.sg3_filtered_lrelu(ctypes.byref(p), abi.stream_ptr(x.device))
         if abi.check(rc, 'sg3_filtered_lrelu', allow_no_kernel=True) == abi.SG3_NO_KERNEL:

@@ -96,6 +96,44 @@ def test_shape_errors_and_kernel_table():
     assert lib.sg3_modconv_packed_floats(81, 128, 3, _sg3abi.SG3_CONV_F16) == 81 * 8 * 9 * 16       # same packing as f16x3
 
 
+def _stream_grid(n, c, x, up, down, fu, fd, pad, read=False, write=False):
+    """sg3_filtered_lrelu_stream_grid of a square separable call on dense fp32 planes (host only: no pointer is followed)."""
+    from torch_utils import _sg3abi
+    lib = _sg3abi.load()
+    out = [ctypes.c_int() for _ in range(5)]
+    assert lib.sg3_filtered_lrelu_shape(x, x, up, down, fu, 0, fd, 0, pad[0], pad[1], pad[0], pad[1], *[ctypes.byref(o) for o in out]) == 0
+    p = _sg3abi.FilteredLreluParams()
+    p.dtype = _sg3abi.SG3_F32
+    p.N, p.C, p.xH, p.xW, p.yH, p.yW = n, c, x, x, out[0].value, out[1].value
+    for i, v in enumerate((c * x * x, x * x, x, 1)):
+        p.xStride[i] = v
+    for i, v in enumerate((c * p.yH * p.yW, p.yH * p.yW, p.yW, 1)):
+        p.yStride[i] = v
+    p.up, p.down, p.fuW, p.fdW, p.px0, p.py0 = up, down, fu, fd, pad[0], pad[0]
+    p.gain, p.slope, p.clamp = 1.4142135, 0.2, 256.0
+    p.readSigns, p.writeSigns = int(read), int(write)
+    if read or write:
+        p.s, p.sH, p.sWbytes = 16, out[2].value, out[3].value            # a non-null placeholder: the query follows no pointer
+    g = [ctypes.c_int() for _ in range(5)]
+    ok = lib.sg3_filtered_lrelu_stream_grid(ctypes.byref(p), *[ctypes.byref(v) for v in g])
+    return (ok, p.yH) + tuple(v.value for v in g)
+
+
+def test_filtered_lrelu_stream_grid():
+    """The decomposition query answers from the launch's own functions: (ok, yH, nStrips, stripW, nFullStrips, nChunks, chunkRows)."""
+    # T-1024 L13 (1046 -> 1024, 32 channels): 9 equal strips; batch 1 takes the yH / 48 cap, batch 4 chunks of 69 rows
+    assert _stream_grid(1, 32, 1046, 2, 2, 12, 12, (-11, -12), write=True) == (1, 1024, 9, 114, 0, 21, 49)
+    assert _stream_grid(4, 32, 1046, 2, 2, 12, 12, (-11, -12), write=True)[5:] == (15, 69)
+    # 148 columns = one full strip + a 28-column remainder with two planes per wave: plain forward only
+    assert _stream_grid(1, 512, 150, 2, 2, 12, 12, (9, 8))[2:5] == (2, 120, 1)
+    assert _stream_grid(1, 512, 150, 2, 2, 12, 12, (9, 8), write=True)[2:5] == (2, 74, 0)
+    # adjoint of an up-4 layer: up 2 / down 4, strips of at most 58 columns
+    ok, yh, ns, tw, nfull, nc, ch = _stream_grid(1, 32, 1024, 2, 4, 12, 24, (20, 35), read=True)
+    assert ok == 1 and tw <= 58 and ns == -(-yh // 58) and nfull == 0 and nc * ch >= yh > (nc - 1) * ch
+    # ToRGB's pointwise call is not a streaming-kernel call
+    assert _stream_grid(1, 3, 1024, 1, 1, 1, 1, (0, 0))[0] == 0
+
+
 def test_gpu_tensor_without_library_raises(monkeypatch, tmp_path):
     """The product never falls back silently: a missing library is a RuntimeError."""
     from torch_utils import _sg3abi

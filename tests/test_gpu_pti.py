@@ -74,7 +74,9 @@ def _layer_cases(cfg, names):
 def test_pti_filter_kernels_at_1024_geometry(cfg, names):
     """The 1024^2 sign-writing forward and sign-reading adjoint (the PTI path of BASELINE configs[3]) on a cropped plane set
     (2 channels of the real layer geometry: the kernels treat planes independently): output, dx and db against autograd through
-    the reference formulation on the CPU (`impl='ref'`, reference filtered_lrelu.py:122-154)."""
+    the reference formulation on the CPU (`impl='ref'`, reference filtered_lrelu.py:122-154).
+    The two-plane crop runs 21 row chunks (the yH / 48 cap); the real plane counts of batch 1 and 4, with their own chunk heights,
+    are covered against float64 in test_gpu_flrelu_fp64.py."""
     from golden_cases import rand
     from torch_utils.ops import filtered_lrelu as fl
     for name, side, up, pad, fu, fd in _layer_cases(cfg, names):
