@@ -129,6 +129,13 @@ SG3_API int sg3_filtered_lrelu_finish_partials(const float* sumPartial, const fl
  * 0 when the call does not take the streaming kernel.  For tests and profiling; no reference counterpart. */
 SG3_API int sg3_filtered_lrelu_planes_per_wave(const sg3_filtered_lrelu_params* p);
 
+/* Diagnostic: the up-4 separable plain forward (fp32 / fp16) has two forms with bit-identical outputs -- the default, which holds
+ * its up taps in scalar registers and single vector register pairs and runs four waves per SIMD, and the earlier, wider one (three
+ * waves).  wide != 0 routes every later up-4 launch of the process to the earlier form, 0 back to the default; returns the previous
+ * setting.  A process setting made by an explicit call (the bit-identity test, A/B timing) -- not an environment variable read per
+ * launch, which could differ between a graph capture and a later eager call.  SG3_FLRELU_UP4_WIDE=1 in the environment seeds it once. */
+SG3_API int sg3_filtered_lrelu_force_up4_wide(int wide);
+
 /* Host-only query: the work decomposition `sg3_filtered_lrelu` launches for this call, from the functions the launch itself uses.
  * Output rows are cut into nChunks chunks of chunkRows rows (the last one shorter); output columns into nStrips strips: equal strips
  * of stripW columns (nFullStrips = 0), or nFullStrips strips of stripW = 120 columns, one plane per wave, followed by one remainder

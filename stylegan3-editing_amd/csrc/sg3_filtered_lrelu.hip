@@ -43,6 +43,7 @@
 //
 // Algorithmic traffic: C*(xH*xW + yH*yW)*sizeof(T) bytes per image -- the roofline figure bench.py uses.
 #include "sg3_common.h"
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
 
@@ -101,6 +102,16 @@ __device__ __forceinline__ float to_sgpr(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
 }
 
+// A wave-uniform value the compiler must keep in a scalar register.  `to_sgpr` does not do that for a value formed by a vector
+// instruction (a tap times `up`: gfx950 has no scalar float multiply): the compiler proves it uniform, folds the readfirstlane
+// away and leaves the value in a VGPR for the whole kernel.  The s_nop is the wait state a v_readfirstlane needs after the vector
+// instruction that wrote its source; the compiler inserts it around its own, not inside an asm statement.
+__device__ __forceinline__ float pin_sgpr(float v) {
+    float r;
+    asm("s_nop 1\n\tv_readfirstlane_b32 %0, %1" : "=s"(r) : "v"(v));
+    return r;
+}
+
 // Compiler-level ordering of this wave's LDS traffic (no instruction is emitted: a wave's DS ops execute in order).
 __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -126,6 +137,27 @@ __device__ __forceinline__ v2f mul_tap(v2f a, v2f tapPair) {
     if (HALF == 0) return a * __builtin_shufflevector(tapPair, tapPair, 0, 0);
     v2f r;
     asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(r) : "v"(a), "s"(tapPair));
+    return r;
+}
+// The same two operations with the register file of the tap pair stated (VREG: a vector register pair) and BOTH halves selected by
+// op_sel.  Left to the compiler, the low half of a pair that sits in vector registers is splatted into a second register pair per
+// tap: at up 4 the 24 up taps then hold 48 VGPRs, and the kernel loses its fourth wave per SIMD.
+template <int HALF, bool VREG>
+__device__ __forceinline__ v2f fma_tap_at(v2f a, v2f tapPair, v2f acc) {
+    v2f r;
+    if (HALF == 0 && VREG)  asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,0,1]" : "=v"(r) : "v"(a), "v"(tapPair), "v"(acc));
+    if (HALF == 0 && !VREG) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,0,1]" : "=v"(r) : "v"(a), "s"(tapPair), "v"(acc));
+    if (HALF == 1 && VREG)  asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "=v"(r) : "v"(a), "v"(tapPair), "v"(acc));
+    if (HALF == 1 && !VREG) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "=v"(r) : "v"(a), "s"(tapPair), "v"(acc));
+    return r;
+}
+template <int HALF, bool VREG>
+__device__ __forceinline__ v2f mul_tap_at(v2f a, v2f tapPair) {
+    v2f r;
+    if (HALF == 0 && VREG)  asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(r) : "v"(a), "v"(tapPair));
+    if (HALF == 0 && !VREG) asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(r) : "v"(a), "s"(tapPair));
+    if (HALF == 1 && VREG)  asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(r) : "v"(a), "v"(tapPair));
+    if (HALF == 1 && !VREG) asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(r) : "v"(a), "s"(tapPair));
     return r;
 }
 
@@ -294,10 +326,19 @@ __host__ __device__ static inline float fast_threshold(const float* fu, int taps
 // 2k + 1, with their own segments of the two LDS rows -- the 36^2 .. 52^2 layers use 21 .. 29 lanes of a wave otherwise, and the
 // kernel's time there is its instruction count.  Plain forward only; tensors dense over (n, c) so that plane 2k + 1 sits one
 // channel stride after plane 2k (also across the end of an image).
-template <typename T, int U, int D, int VPH, int RADIAL, int SIGNS, int G = 1>
+// WIDE: 1 = the up-4 separable plain forward as it was before its up taps were placed by hand (141 .. 147 VGPRs, three waves per
+// SIMD): kept for A/B timing and the bit-identity test (`stream_up4_wide`).  The default form computes the same products in the same
+// order from the same tap values; only the registers that hold the taps differ.
+template <typename T, int U, int D, int VPH, int RADIAL, int SIGNS, int G = 1, int WIDE = 0>
 struct Stream {
     typedef StreamCfg<U, D> Cfg;
     typedef WaveState<T, U, D> State;
+    static_assert(WIDE == 0 || (U == 4 && RADIAL == 0 && SIGNS == 0), "WIDE: the up-4 separable plain forward only");
+    // Up-4 separable plain forward: where the 12 up tap pairs live.  The scalar file has room for half of them next to the 6 down
+    // tap pairs, the descriptors and the row bookkeeping (all 12: 51 .. 62 scalar spills, v_readlane in the row loop); the first
+    // TU_PIN pairs are pinned there, the others sit in 12 VGPRs, one pair each, both halves read through op_sel.
+    static constexpr bool PLACED = U == 4 && RADIAL == 0 && SIGNS == 0 && WIDE == 0;
+    static constexpr int TU_PIN = PLACED ? 6 : 0;
 
     // issue the loads of input row `i` into st.pre[slot]; rows outside the image get a zero-length descriptor
     static __device__ __forceinline__ void prefetch(State& st, int slot, const StreamParams& p, const T* __restrict__ plane,
@@ -460,6 +501,23 @@ struct Stream {
                 const int slot = (S + 1 + t) % 6;              // t = 0: oldest row (i - 5)
                 const int k = kv + U * t;
                 // tap k lives in the reversed pair k/2: odd k = low half, even k = high half
+                if (PLACED) {
+                    const v2f tp = st.tuP[k / 2];
+                    const bool vr = k / 2 >= TU_PIN;
+                    if (t == 0) {
+                        u0 = (k & 1) ? (vr ? mul_tap_at<0, true>(st.w[slot][0], tp) : mul_tap_at<0, false>(st.w[slot][0], tp))
+                                     : (vr ? mul_tap_at<1, true>(st.w[slot][0], tp) : mul_tap_at<1, false>(st.w[slot][0], tp));
+                        u1 = (k & 1) ? (vr ? mul_tap_at<0, true>(st.w[slot][1], tp) : mul_tap_at<0, false>(st.w[slot][1], tp))
+                                     : (vr ? mul_tap_at<1, true>(st.w[slot][1], tp) : mul_tap_at<1, false>(st.w[slot][1], tp));
+                    } else if (k & 1) {
+                        u0 = vr ? fma_tap_at<0, true>(st.w[slot][0], tp, u0) : fma_tap_at<0, false>(st.w[slot][0], tp, u0);
+                        u1 = vr ? fma_tap_at<0, true>(st.w[slot][1], tp, u1) : fma_tap_at<0, false>(st.w[slot][1], tp, u1);
+                    } else {
+                        u0 = vr ? fma_tap_at<1, true>(st.w[slot][0], tp, u0) : fma_tap_at<1, false>(st.w[slot][0], tp, u0);
+                        u1 = vr ? fma_tap_at<1, true>(st.w[slot][1], tp, u1) : fma_tap_at<1, false>(st.w[slot][1], tp, u1);
+                    }
+                    continue;
+                }
                 if (t == 0) {
                     u0 = (k & 1) ? mul_tap<0>(st.w[slot][0], st.tuP[k / 2]) : mul_tap<1>(st.w[slot][0], st.tuP[k / 2]);
                     u1 = (k & 1) ? mul_tap<0>(st.w[slot][1], st.tuP[k / 2]) : mul_tap<1>(st.w[slot][1], st.tuP[k / 2]);
@@ -790,7 +848,8 @@ struct Stream {
         for (int m = 0; m < Cfg::FU / 2; m++) {
             if (UP2D) { st.tuP[m] = splat(0.f); continue; }          // 2-D up filter: rows stream from the scalar cache
             const float f1 = p.fu[p.flip ? 2 * m + 1 : Cfg::FU - 2 - 2 * m], f0 = p.fu[p.flip ? 2 * m : Cfg::FU - 1 - 2 * m];
-            st.tuP[m] = (v2f){to_sgpr(f1 * gU), to_sgpr(f0 * gU)};
+            if (m < TU_PIN) st.tuP[m] = (v2f){pin_sgpr(f1 * gU), pin_sgpr(f0 * gU)};
+            else st.tuP[m] = (v2f){to_sgpr(f1 * gU), to_sgpr(f0 * gU)};
         }
         if (RDOWN) {
 #pragma unroll
@@ -892,10 +951,10 @@ struct Stream {
     }
 };
 
-template <typename T, int U, int D, int VPH, int RADIAL, int SIGNS, int G = 1>
+template <typename T, int U, int D, int VPH, int RADIAL, int SIGNS, int G = 1, int WIDE = 0>
 __global__ void __launch_bounds__(64)
 flrelu_stream_kernel(StreamParams p) {
-    Stream<T, U, D, VPH, RADIAL, SIGNS, G>::run(p);
+    Stream<T, U, D, VPH, RADIAL, SIGNS, G, WIDE>::run(p);
 }
 
 // ---------------------------------------------------------------------------
@@ -996,6 +1055,14 @@ static bool stream_fast_activation(const sg3_filtered_lrelu_params& q) {
     return !(e && e[0] == '1') && !q.readSigns && !q.writeSigns && q.gain > 0.f && q.gain < INFINITY && q.clamp >= 0.f;
 }
 
+// The up-4 separable plain forward has two forms that compute the same thing bit for bit: the default (up taps placed by hand, at
+// most 128 VGPRs, four waves per SIMD) and the earlier one (`Stream`'s WIDE).  A process setting, seeded ONCE from the environment
+// (SG3_FLRELU_UP4_WIDE=1: A/B timing) and changed only by an explicit sg3_filtered_lrelu_force_up4_wide call (the bit-identity test).
+static std::atomic<int> g_up4_wide{[] { const char* e = getenv("SG3_FLRELU_UP4_WIDE"); return (e && e[0] == '1') ? 1 : 0; }()};
+static bool stream_up4_wide(const sg3_filtered_lrelu_params& q) {
+    return q.up == 4 && q.fdH == 0 && !q.readSigns && !q.writeSigns && g_up4_wide.load(std::memory_order_relaxed) != 0;
+}
+
 // width of the full strips when a row is cut into full strips + a packed remainder, and their number (0: equal strips instead --
 // no remainder, a remainder too wide to pack, or more waves than equal strips take)
 constexpr int STREAM_FULL_TW = 120;
@@ -1065,7 +1132,7 @@ static int launch_stream(const sg3_filtered_lrelu_params& q, hipStream_t st) {
     const int remFull = stream_full_strips(q.yW, p.nStrips);
     const bool mixed = !packed && remFull > 0 && stream_packs_planes(q, q.yW - remFull * STREAM_FULL_TW);
     // ONE launch of the two-plane kernel, whose first blocks take the full strips, where it holds as many waves per SIMD as the
-    // one-plane kernel (separable: 120 / 124 registers at up 2, 142 / 144 at up 4; 12x12 down filter at up 4: 153 .. 160 against
+    // one-plane kernel (separable: 120 / 124 registers at up 2, 104 / 111 at up 4 -- 142 / 147 in the WIDE form; 12x12 down filter at up 4: 153 .. 160 against
     // 148 .. 156, three waves either way).  12x12 down filter at up 2: two launches (135 registers against 128: three waves, not four)
     const bool oneLaunch = mixed && (q.fdH == 0 || q.up == 4);
     p.wideBlocks = 0;
@@ -1082,7 +1149,11 @@ static int launch_stream(const sg3_filtered_lrelu_params& q, hipStream_t st) {
     }
 
     const int vph = (((q.py0 - (q.up - 1)) % q.down) + q.down) % q.down;
+    const bool up4Wide = stream_up4_wide(q);
     dim3 g((unsigned)p.totalBlocks), b(64);
+#define SG3_UP4_WIDE_LAUNCH(GG) do { \
+        if (vph == 0) hipLaunchKernelGGL((flrelu_stream_kernel<T, 4, 2, 0, 0, 0, GG, 1>), g, b, 0, st, p); \
+        else hipLaunchKernelGGL((flrelu_stream_kernel<T, 4, 2, 1, 0, 0, GG, 1>), g, b, 0, st, p); } while (0)
 #define SG3_STREAM_LAUNCH(U, D, V, R, S) hipLaunchKernelGGL((flrelu_stream_kernel<T, U, D, V, R, S>), g, b, 0, st, p)
 #define SG3_STREAM_LAUNCH_V(U, R, S) do { if (vph == 0) SG3_STREAM_LAUNCH(U, 2, 0, R, S); else SG3_STREAM_LAUNCH(U, 2, 1, R, S); } while (0)
 #define SG3_PACKED_LAUNCH(U, V, R) hipLaunchKernelGGL((flrelu_stream_kernel<T, U, 2, V, R, 0, 2>), g, b, 0, st, p)
@@ -1114,17 +1185,18 @@ static int launch_stream(const sg3_filtered_lrelu_params& q, hipStream_t st) {
     } else if (q.writeSigns) {
         SG3_FORWARD_LAUNCH(1);
     } else if (packed || oneLaunch) {
-        if (q.up == 2) SG3_PACKED_UP(2); else SG3_PACKED_UP(4);
+        if (up4Wide) SG3_UP4_WIDE_LAUNCH(2); else if (q.up == 2) SG3_PACKED_UP(2); else SG3_PACKED_UP(4);
     } else {
-        SG3_FORWARD_LAUNCH(0);
+        if (up4Wide) SG3_UP4_WIDE_LAUNCH(1); else SG3_FORWARD_LAUNCH(0);
         if (mixed) {
             SG3_LAUNCH_CHECK("flrelu_stream_kernel");
             p.ox0Base = remFull * STREAM_FULL_TW; p.nStrips = 1; p.TW = q.yW - p.ox0Base;
             p.totalBlocks = (int)((planes + 1) / 2 * p.nChunks);
             g = dim3((unsigned)p.totalBlocks);
-            if (q.up == 2) SG3_PACKED_UP(2); else SG3_PACKED_UP(4);
+            if (up4Wide) SG3_UP4_WIDE_LAUNCH(2); else if (q.up == 2) SG3_PACKED_UP(2); else SG3_PACKED_UP(4);
         }
     }
+#undef SG3_UP4_WIDE_LAUNCH
 #undef SG3_PACKED_UP
 #undef SG3_PACKED_LAUNCH_V
 #undef SG3_PACKED_LAUNCH
@@ -1208,6 +1280,8 @@ float sg3_filtered_lrelu_fast_threshold(const float* fu, int fuW, int up, float 
     if (!fu || up < 1 || fuW < up) return -1.f;
     return sg3::fast_threshold(fu, fuW, up, gain, slope, clamp);
 }
+
+int sg3_filtered_lrelu_force_up4_wide(int wide) { return sg3::g_up4_wide.exchange(wide ? 1 : 0); }
 
 int sg3_filtered_lrelu_planes_per_wave(const sg3_filtered_lrelu_params* p) {
     using namespace sg3;

@@ -132,6 +132,7 @@ EXPORTS = [
     ('sg3_device_count', ctypes.c_int, []),
     ('sg3_filtered_lrelu', ctypes.c_int, [ctypes.POINTER(FilteredLreluParams), c_vp]),
     ('sg3_filtered_lrelu_planes_per_wave', ctypes.c_int, [ctypes.POINTER(FilteredLreluParams)]),
+    ('sg3_filtered_lrelu_force_up4_wide', ctypes.c_int, [ctypes.c_int]),
     ('sg3_filtered_lrelu_stream_grid', ctypes.c_int, [ctypes.POINTER(FilteredLreluParams)] + [ctypes.POINTER(ctypes.c_int)] * 5),
     ('sg3_filtered_lrelu_fast_threshold', ctypes.c_float, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float]),
     ('sg3_filtered_lrelu_has_kernel', ctypes.c_int, [ctypes.c_int] * 6),
