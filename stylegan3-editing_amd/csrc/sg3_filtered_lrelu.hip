@@ -119,6 +119,21 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// a + b as ONE v_add_f32, hidden from the SLP vectoriser (sg3_split.h `mul_single` is the same device for a multiply)
+__device__ __forceinline__ float add_single(float a, float b) {
+    float r;
+    asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
+// max(m, |a|, |b|) that PROPAGATES a NaN (IEEE 754-2019 maximum; v_max3_f32 returns the other operand).  asm: the file is built
+// with -fno-honor-nans, under which the compiler may trade it for the form that drops the NaN
+__device__ __forceinline__ float max3_abs_nan(float m, float a, float b) {
+    float r;
+    asm("v_maximum3_f32 %0, %1, |%2|, |%3|" : "=v"(r) : "v"(m), "v"(a), "v"(b));
+    return r;
+}
+
 __device__ __forceinline__ v2f fma2(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ v2f splat(float a) { return (v2f){a, a}; }
 
@@ -295,6 +310,7 @@ struct WaveState {
     unsigned sg[SG3_PREFETCH_ROWS][U];       // sign-read mode: prefetched sign bytes (this lane's byte | next byte << 8) per upsampled row
     float osum;                   // running sum of the outputs this lane stored (only kept when p.ysum is given)
     float omax;                   // running max |output| (only kept when p.ymax is given)
+    float xmax;                   // separable plain forward, fast pass: running max |staged sample| of this lane, NaN once it staged one
     int soff;                     // sign modes: byte offset, inside a sign row, of the byte holding this lane's first column
     int sq;                       // sign modes: position (0..3) of that column inside its byte (wave-uniform)
     int inBase, outBase;          // packed mode: this lane's window start in the input LDS row / its 4 samples' place in the output LDS row
@@ -339,6 +355,8 @@ struct Stream {
     // TU_PIN pairs are pinned there, the others sit in 12 VGPRs, one pair each, both halves read through op_sel.
     static constexpr bool PLACED = U == 4 && RADIAL == 0 && SIGNS == 0 && WIDE == 0;
     static constexpr int TU_PIN = PLACED ? 6 : 0;
+    // separable plain forward (either up factor, one or two planes per wave): the forms whose bookkeeping is trimmed by hand
+    static constexpr bool PLAIN = RADIAL == 0 && SIGNS == 0 && WIDE == 0;
 
     // issue the loads of input row `i` into st.pre[slot]; rows outside the image get a zero-length descriptor
     static __device__ __forceinline__ void prefetch(State& st, int slot, const StreamParams& p, const T* __restrict__ plane,
@@ -348,10 +366,25 @@ struct Stream {
         // packed: the descriptor spans the same row of both planes (the lanes' offsets carry the plane and the column range check)
         const int rowBytes = (G > 1 ? (int)p.xsC + p.xW : p.xW) * (int)sizeof(T);
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)row, (short)0, rowOk ? rowBytes : 0, 0x00020000);
-        const float rowFlag = rowOk ? 1.f : 0.f;
+        float rowFlag = rowOk ? 1.f : 0.f;
+        if (PLAIN) {
+            // the flag as ONE scalar register (s_cselect on its bits) that the multiply-add reads as it stands.  Left visible, the
+            // compiler selects the bias per lane instead (v_cndmask per load, and the add besides).  Same operation, same bits.
+            int rowBits = rowOk ? 0x3f800000 : 0;
+            asm("" : "+s"(rowBits));
+            rowFlag = __builtin_bit_cast(float, rowBits);
+        }
 #pragma unroll
-        for (int q = 0; q < Cfg::NL; q++)
+        for (int q = 0; q < Cfg::NL; q++) {
+            if (PLAIN && q + 1 < Cfg::NL) {          // two loads, one packed multiply-add
+                const v2f ld = {bufio<T>::ld(rs, st.coff[q]), bufio<T>::ld(rs, st.coff[q + 1])};
+                const v2f r = fma2((v2f){st.bcol[q], st.bcol[q + 1]}, splat(rowFlag), ld);
+                st.pre[slot][q] = r.x; st.pre[slot][q + 1] = r.y;
+                q++;
+                continue;
+            }
             st.pre[slot][q] = __builtin_fmaf(st.bcol[q], rowFlag, bufio<T>::ld(rs, st.coff[q]));
+        }
         if (SIGNS == 2) {
             // sign bytes of the U upsampled rows this input row will complete (rows / bytes outside the tensor read 0)
 #pragma unroll
@@ -368,8 +401,9 @@ struct Stream {
     }
 
     // one input row: H-up into window slot S, then U upsampled rows through lrelu into the down accumulators.  FAST (plain forward
-    // only): the activation is the single med3(u, slope u, clamp), and `liveGain` drops to 0 from the row in which a staged sample
-    // failed |x| <= fastT (the outputs of such a pass are rewritten by a pass with FAST = false)
+    // only): the activation is the single med3(u, slope u, clamp), and a staged sample that fails |x| <= fastT is recorded -- in
+    // st.xmax (separable forms), or by `liveGain` dropping to 0 from that row on (radial and WIDE forms) -- so that the outputs of
+    // such a pass are rewritten by a pass with FAST = false
     template <int S, bool FAST>
     static __device__ __forceinline__ void step(State& st, const StreamParams& p, const T* __restrict__ plane, T* __restrict__ oplane,
                                                 unsigned char* __restrict__ splane, lds_f* sIn, lds_f* sOut, int i, int delta, int lane,
@@ -391,7 +425,14 @@ struct Stream {
         // scalar register, overwritten in place -- is NaN: every output it still writes in this strip is NaN.  That is a superset of the
         // reference's NaN footprint (a failure stays loud and stays where it happened), at no cost inside the nonlinearity.  The
         // last load of a row holds the strip's 6 halo samples, which the neighbouring strip classifies as its own: left out here.
-        if (SIGNS == 0 && FAST) {
+        if (PLAIN && FAST) {
+            // fast pass: the threshold test needs its answer only when the chunk is done (`run` reads it once), so a lane folds the
+            // samples it stages -- the strip's halo included: it feeds this strip's upsampled samples -- into a running maximum of
+            // magnitudes that keeps a NaN, two samples per instruction, instead of comparing each load against the threshold
+#pragma unroll
+            for (int q = 0; q < Cfg::NL; q += 2)
+                st.xmax = max3_abs_nan(st.xmax, st.pre[PS][q], st.pre[PS][q + 1 < Cfg::NL ? q + 1 : q]);
+        } else if (SIGNS == 0 && FAST) {
             // fast pass: every load a lane stages, the strip's halo included (it feeds this strip's upsampled samples), is tested
             // against the threshold: v_cmp_nle is true for |x| > T, NaN and infinity alike, and takes the place of the class test.
             // The radial forms have no scalar register to spare (a spill puts v_readlane into the row loop): T sits in a VGPR there.
@@ -459,7 +500,7 @@ struct Stream {
         const float slope = p.slope, clampv = p.clamp / p.gain, gain = p.gain;
         // the 2-D up filter's taps carry no up^2 factor
         const float gainOut = UP2D ? p.gain * (float)(U * U) :
-                              ((SIGNS <= 1 && (SG3_NAN_GUARD || FAST)) ? ((G > 1 && lane >= 32 && !FAST) ? liveGain1 : liveGain) : p.gain);
+                              ((SIGNS <= 1 && (SG3_NAN_GUARD || FAST) && !(PLAIN && FAST)) ? ((G > 1 && lane >= 32 && !FAST) ? liveGain1 : liveGain) : p.gain);
 #pragma unroll
         for (int j = 0; j < U; j++) {
             const int kv = U - 1 - j;                          // vertical up phase of this row
@@ -704,7 +745,10 @@ struct Stream {
                         v2f y0 = pr[0] * st.tdP[0], y1 = pr[1] * st.tdP[0];
 #pragma unroll
                         for (int q = 1; q < Cfg::FD / 2; q++) { y0 = fma2(pr[q], st.tdP[q], y0); y1 = fma2(pr[q + 1], st.tdP[q], y1); }
-                        const float f0 = (y0.x + y0.y) * gainOut, f1 = (y1.x + y1.y) * gainOut;
+                        // even + odd phase of each column.  Written as y0.x + y0.y the two sums become one packed add whose operands
+                        // are first re-packed across register pairs (three v_mov per output row); two plain adds need no move
+                        const float e0 = PLAIN ? add_single(y0.x, y0.y) : y0.x + y0.y, e1 = PLAIN ? add_single(y1.x, y1.y) : y1.x + y1.y;
+                        const float f0 = e0 * gainOut, f1 = e1 * gainOut;
                         if (SIGNS == 2) {
                             const float m0 = 2 * lane < oxN ? f0 : 0.f, m1 = 2 * lane + 1 < oxN ? f1 : 0.f;
                             st.osum += m0 + m1;
@@ -894,6 +938,7 @@ struct Stream {
 
         st.osum = 0.f;
         st.omax = 0.f;
+        st.xmax = 0.f;
         float liveGain = p.gain;                  // the output gain; NaN from the row on in which this wave staged a non-finite sample
         float liveGain1 = p.gain;                 // packed mode: the second plane's
         if (SIGNS) {
@@ -916,7 +961,8 @@ struct Stream {
         // (a wave-uniform choice made once, before the row loop: a branch inside it costs 5 %); a wave that met a sample above it --
         // or a NaN, or an infinity -- runs the chunk again with lrelu + clamp and the NaN guard, rewriting every output it stored.
         // Either way the outputs are those of the second form, bit for bit.
-        // The fast pass's output gain is its flag (0 from the row of a failed test on; fastAct promises a finite positive gain).
+        // The fast pass's flag: the lanes' running maximum |staged sample| against the threshold (separable forms); its output gain,
+        // 0 from the row of a failed test on (radial and WIDE forms; fastAct promises a finite positive gain).
         bool slow = true;
         if constexpr (SIGNS == 0) {
             const float fastT = p.fastAct ? to_sgpr(fast_threshold(p.fu, Cfg::FU, U, p.gain, p.slope, p.clamp)) : -1.f;
@@ -924,7 +970,14 @@ struct Stream {
                 float fastGain = p.gain, unused = p.gain;
                 stream_chunk<true>(st, p, plane, oplane, splane, sIn, sOut, iFirst, nBlocks, delta, lane, oy0, oy1, ox0, oxN, pairStore, fastGain,
                                    unused, wide, fastT);
-                slow = fastGain != p.gain;
+                if (PLAIN) {
+                    // |x| <= T on every sample every lane staged?  v_cmp_nle is true for a maximum above T, an infinity and a NaN alike
+                    unsigned long long m;
+                    asm("v_cmp_nle_f32_e64 %0, %1, %2" : "=s"(m) : "v"(st.xmax), "s"(fastT));
+                    slow = m != 0ull;
+                } else {
+                    slow = fastGain != p.gain;
+                }
             }
         }
         if (slow)
