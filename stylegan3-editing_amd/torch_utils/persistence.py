@@ -5,7 +5,11 @@ Official StyleGAN3 `.pkl` files store, for every persistent object, a dict
 and name `torch_utils.persistence._reconstruct_persistent_obj` as the unpickling function (reference
 torch_utils/persistence.py:119-127, 180-203).  Unpickling therefore execs the embedded NVIDIA module source, which
 imports `torch_utils.misc`, `torch_utils.persistence`, `torch_utils.ops.*` and `dnnlib` BY THOSE NAMES -- that is
-what makes this package layout part of the drop-in contract: the embedded graph code then runs on the HIP kernels.
+what makes this package layout part of the drop-in contract.  The embedded graph code reaches this package's operators
+only: its `filtered_lrelu` and `bias_act` run on the HIP kernels, its convolutions go through `conv2d_gradfix` to the
+library.  This module rebuilds what the pickle says and nothing else; putting a foreign `Generator` onto the native graph
+(HIP modulated convolution, batched preparation, graph capture) is `models.stylegan3.model.adopt_generator`, which
+`SG3Generator` applies to `.pkl` paths by default.
 
 Layout of this module: `_Sources` is the two-way registry module <-> source text; `_PersistentMixin` carries the
 behaviour (remembered constructor arguments, `__reduce__` in the wire format above) and `persistent_class` derives
