@@ -672,6 +672,32 @@ typedef struct sg3_latent_mapper_params {
 
 SG3_API int sg3_latent_mapper(const sg3_latent_mapper_params* p, void* stream);
 
+/* ----------------------------------------------------------------------
+ * CLIP image preprocessing of the StyleCLIP delta_i_c sweep (reference
+ * editing/styleclip_global_directions/preprocess/create_delta_i_c.py:53-56), for x [B,3,H,W] float32:
+ *     y = F.interpolate(x, size=(h, w), mode='bicubic', align_corners=True)
+ *     y = ((y + 1) / 2).clamp(0, 1)
+ *     y = (y - mean[c]) / std[c]                              float32 [B,3,h,w]
+ * in one launch for all B images, one thread per output pixel over the three channels.  Source coordinates are torch's:
+ * scale = float(in - 1) / float(out - 1) (0 when out == 1), src = scale * dst in float32, floorf, t = src - floor; taps are the
+ * cubic convolution with A = -0.75 at floor - 1 .. floor + 2, indices clamped to the border; rows are filtered along x first, then
+ * the four row results along y.  When neither size changes the pixels are copied without filtering, as torch's device kernel does.
+ * The tap polynomials and the four-term sums are explicit fused multiply-adds, as torch's device kernel contracts them; nothing
+ * else is fused (the library is built without contraction for this entry); NaN propagates through the clamp as it does through
+ * torch.clamp.  Strides are in elements (n, c, y, x), any layout; y must not overlap x.  C must be 3, std non-zero.
+ * ---------------------------------------------------------------------- */
+typedef struct sg3_clip_preprocess_params {
+    const float*   x;              /* [B,C,H,W] */
+    int64_t        xStride[4];
+    float*         y;              /* [B,C,h,w] */
+    int64_t        yStride[4];
+    int32_t        B, C, H, W, h, w;
+    float          mean[3];
+    float          std[3];
+} sg3_clip_preprocess_params;
+
+SG3_API int sg3_clip_preprocess(const sg3_clip_preprocess_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -125,6 +125,11 @@ class LatentMapperParams(ctypes.Structure):
                 ('alpha', c_f32)]
 
 
+class ClipPreprocessParams(ctypes.Structure):
+    _fields_ = [('x', c_vp), ('xStride', c_i64 * 4), ('y', c_vp), ('yStride', c_i64 * 4),
+                ('B', c_i32), ('C', c_i32), ('H', c_i32), ('W', c_i32), ('h', c_i32), ('w', c_i32), ('mean', c_f32 * 3), ('std', c_f32 * 3)]
+
+
 # every symbol include/sg3_ops.h declares: (name, restype, argtypes)
 EXPORTS = [
     ('sg3_abi_version', ctypes.c_int, []),
@@ -168,6 +173,7 @@ EXPORTS = [
     ('sg3_resample_coeffs', ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, c_vp, c_vp]),
     ('sg3_image_finish', ctypes.c_int, [ctypes.POINTER(ImageFinishParams), c_vp]),
     ('sg3_latent_mapper', ctypes.c_int, [ctypes.POINTER(LatentMapperParams), c_vp]),
+    ('sg3_clip_preprocess', ctypes.c_int, [ctypes.POINTER(ClipPreprocessParams), c_vp]),
 ]
 
 _lib = None
