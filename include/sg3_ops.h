@@ -698,6 +698,87 @@ typedef struct sg3_clip_preprocess_params {
 
 SG3_API int sg3_clip_preprocess(const sg3_clip_preprocess_params* p, void* stream);
 
+/* ----------------------------------------------------------------------
+ * CLIP ViT encoders (reference models/styleganxl/feature_networks/clip/model.py:153-236, :324-352): the kernels one
+ * ResidualAttentionBlock and the two stems are made of.  The residual stream is float32 [rows][D]; GEMM operands are float16 with
+ * float32 accumulation in ascending k, one accumulator per output element (no split-K, no atomics), so every output row depends
+ * on its own input row only.  One launch per call, on `stream`; every argument check is made on the host before the launch.
+ *
+ * sg3_clip_supported (host only): 1 when these kernels run a transformer of this width, head count and sequence length
+ * (width == 64 * heads, 1 <= L <= 128), else 0.
+ *
+ * sg3_clip_layernorm: out[r][:] = (x[r][:] - mean) / sqrt(var + eps) * gamma + beta, biased variance, float32 statistics taken
+ *   relative to the row's first element (no cancellation on a large mean).  Row r of x starts at x + r * xRowStride (elements);
+ *   out is dense [rows][D] in outDtype (SG3_F16 or SG3_F32); out == x is allowed for SG3_F32 with xRowStride == D.
+ *
+ * sg3_clip_gemm: C[M][N] = A[M][K] . W[N][K]^T (+ bias[N], float32, may be NULL); A and W float16, K contiguous, 16-byte aligned;
+ *   W is nn.Linear's [out][in].  N % 64 == 0 and K % 32 == 0, else SG3_BAD_ARG; M is arbitrary.  epilogue:
+ *     SG3_CLIP_EPI_F32            out float32 [M][N] = acc + bias
+ *     SG3_CLIP_EPI_F16            out float16 [M][N] = acc + bias
+ *     SG3_CLIP_EPI_QUICKGELU_F16  out float16 [M][N] = v * sigmoid(1.702 v), v = acc + bias, in float32
+ *     SG3_CLIP_EPI_RESIDUAL       out float32 [M][N] += acc + bias (in place on the residual stream)
+ *     SG3_CLIP_EPI_PATCH          the patch embedding: a is the dense float32 image [B][3][R][R], 16-byte aligned, R % 4 == 0; w is
+ *                                 conv1.weight [N][3*P*P] in float16, P % 8 == 0, K == 3*P*P; with g = R / P, M == B*g*g and row
+ *                                 m is patch (m / g^2, (m % g^2) / g, m % g).  out float32 [B][g*g + 1][N]: token 1 + patch =
+ *                                 acc + bias + pos[1 + patch], token 0 = cls + pos[0]  (pos [g*g + 1][N], cls [N], float32).
+ *
+ * sg3_clip_attention: qkv float16 [B][L][3*D] as the in_proj GEMM writes it (q | k | v, head h in columns 64 h .. 64 h + 63 of
+ *   each), D = 64 * heads.  out float16 [B][L][D] = softmax(q k^T / 8 (+ causal mask)) v per (sample, head); float32 scores,
+ *   max-subtracted float32 softmax, float32 P.V.  causal != 0: query i attends keys j <= i (the reference's -inf upper triangle).
+ *
+ * sg3_clip_embed: out float32 [B][L][D] = table[tokens[b][l]][:] + pos[l][:]; tokens int64, a token outside [0, vocab) is
+ *   clamped into it.
+ * ---------------------------------------------------------------------- */
+#define SG3_CLIP_EPI_F32           0
+#define SG3_CLIP_EPI_F16           1
+#define SG3_CLIP_EPI_QUICKGELU_F16 2
+#define SG3_CLIP_EPI_RESIDUAL      3
+#define SG3_CLIP_EPI_PATCH         4
+
+typedef struct sg3_clip_layernorm_params {
+    const float*   x;              /* row r at x + r * xRowStride */
+    const float*   gamma;          /* [D] */
+    const float*   beta;           /* [D] */
+    void*          out;            /* [rows][D], outDtype */
+    int64_t        xRowStride;
+    int32_t        rows, D;
+    int32_t        outDtype;       /* SG3_F16 or SG3_F32 */
+    float          eps;
+} sg3_clip_layernorm_params;
+
+typedef struct sg3_clip_gemm_params {
+    const void*    a;              /* float16 [M][K]; SG3_CLIP_EPI_PATCH: float32 [B][3][R][R] */
+    const void*    w;              /* float16 [N][K] */
+    const float*   bias;           /* [N] or NULL */
+    void*          out;
+    const float*   pos;            /* SG3_CLIP_EPI_PATCH: [g*g + 1][N] */
+    const float*   cls;            /* SG3_CLIP_EPI_PATCH: [N] */
+    int32_t        M, K, N;
+    int32_t        epilogue;
+    int32_t        P, R;           /* SG3_CLIP_EPI_PATCH: patch size, image resolution */
+} sg3_clip_gemm_params;
+
+typedef struct sg3_clip_attention_params {
+    const void*    qkv;            /* float16 [B][L][3*64*heads] */
+    void*          out;            /* float16 [B][L][64*heads] */
+    int32_t        B, L, heads;
+    int32_t        causal;
+} sg3_clip_attention_params;
+
+typedef struct sg3_clip_embed_params {
+    const int64_t* tokens;         /* [B][L] */
+    const float*   table;          /* [vocab][D] */
+    const float*   pos;            /* [L][D] */
+    float*         out;            /* [B][L][D] */
+    int32_t        B, L, D, vocab;
+} sg3_clip_embed_params;
+
+SG3_API int sg3_clip_supported(int width, int heads, int L);
+SG3_API int sg3_clip_layernorm(const sg3_clip_layernorm_params* p, void* stream);
+SG3_API int sg3_clip_gemm(const sg3_clip_gemm_params* p, void* stream);
+SG3_API int sg3_clip_attention(const sg3_clip_attention_params* p, void* stream);
+SG3_API int sg3_clip_embed(const sg3_clip_embed_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

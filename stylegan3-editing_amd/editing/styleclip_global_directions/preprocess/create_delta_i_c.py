@@ -18,8 +18,9 @@ sits at mean + strength * std, for all samples.  Files made by the reference wer
 The caller's `latents_s` is never written to in either mode.
 
 The CLIP model is external to this package, like the text encoder of `global_direction.py`: `image_encoder` is a callable
-[n,3,224,224] -> [n,D] (CLIP's `encode_image`).  `main` takes an `Options` (no pyrallis CLI) and, as this package has no
-configs/paths_config.py, the options carry the generator path."""
+[n,3,224,224] -> [n,D] (CLIP's `encode_image`).  The package's own CLIP (models/clip, native transformer kernels on the GPU) is
+used when `Options.clip_checkpoint_path` names its state-dict file and no `image_encoder` is passed.  `main` takes an `Options`
+(no pyrallis CLI) and, as this package has no configs/paths_config.py, the options carry the generator path."""
 import pickle
 import warnings
 from dataclasses import dataclass
@@ -51,6 +52,8 @@ class Options:
     results_path: Path = Path("delta_i_c")
     # latents per channel; the reference's authors used 300
     num_samples: int = 1
+    # CLIP state-dict file for the package's own encoder (models.clip.load); used when no image_encoder is passed
+    clip_checkpoint_path: Optional[Path] = None
 
 
 def generate_images(stylegan_model, latents_s, batch_size=1, **synthesis_kwargs):
@@ -153,11 +156,15 @@ def compute_clip_features(G, latents_s, s_mean, s_std, image_encoder, manipulati
 
 
 def main(opts: Options, image_encoder=None, generator=None, max_batch=32, restore=False, shard=False, **synthesis_kwargs):
-    """Writes results_path / clip_features.npy and delta_i_c.npy.  `image_encoder`: see compute_clip_features; when None, CLIP's
-    ViT-B/32 is loaded through the `clip` package.  `generator` replaces loading `opts.checkpoint_path`."""
+    """Writes results_path / clip_features.npy and delta_i_c.npy.  `image_encoder`: see compute_clip_features; when None, the
+    package's CLIP is loaded from `opts.clip_checkpoint_path` if that is set, else CLIP's ViT-B/32 through the `clip` package.
+    `generator` replaces loading `opts.checkpoint_path`."""
     results_path = Path(opts.results_path)
     results_path.mkdir(exist_ok=True, parents=True)
     device = torch.device('cuda' if torch.cuda.is_available() else 'cpu') if generator is None else next(generator.parameters()).device
+    if image_encoder is None and getattr(opts, 'clip_checkpoint_path', None) is not None:
+        from models.clip import load as load_clip
+        image_encoder = load_clip(opts.clip_checkpoint_path, device).encode_image
     if image_encoder is None:
         try:
             import clip

@@ -130,6 +130,27 @@ class ClipPreprocessParams(ctypes.Structure):
                 ('B', c_i32), ('C', c_i32), ('H', c_i32), ('W', c_i32), ('h', c_i32), ('w', c_i32), ('mean', c_f32 * 3), ('std', c_f32 * 3)]
 
 
+SG3_CLIP_EPI_F32, SG3_CLIP_EPI_F16, SG3_CLIP_EPI_QUICKGELU_F16, SG3_CLIP_EPI_RESIDUAL, SG3_CLIP_EPI_PATCH = 0, 1, 2, 3, 4
+
+
+class ClipLayernormParams(ctypes.Structure):
+    _fields_ = [('x', c_vp), ('gamma', c_vp), ('beta', c_vp), ('out', c_vp), ('xRowStride', c_i64), ('rows', c_i32), ('D', c_i32),
+                ('outDtype', c_i32), ('eps', c_f32)]
+
+
+class ClipGemmParams(ctypes.Structure):
+    _fields_ = [('a', c_vp), ('w', c_vp), ('bias', c_vp), ('out', c_vp), ('pos', c_vp), ('cls', c_vp),
+                ('M', c_i32), ('K', c_i32), ('N', c_i32), ('epilogue', c_i32), ('P', c_i32), ('R', c_i32)]
+
+
+class ClipAttentionParams(ctypes.Structure):
+    _fields_ = [('qkv', c_vp), ('out', c_vp), ('B', c_i32), ('L', c_i32), ('heads', c_i32), ('causal', c_i32)]
+
+
+class ClipEmbedParams(ctypes.Structure):
+    _fields_ = [('tokens', c_vp), ('table', c_vp), ('pos', c_vp), ('out', c_vp), ('B', c_i32), ('L', c_i32), ('D', c_i32), ('vocab', c_i32)]
+
+
 # every symbol include/sg3_ops.h declares: (name, restype, argtypes)
 EXPORTS = [
     ('sg3_abi_version', ctypes.c_int, []),
@@ -174,6 +195,11 @@ EXPORTS = [
     ('sg3_image_finish', ctypes.c_int, [ctypes.POINTER(ImageFinishParams), c_vp]),
     ('sg3_latent_mapper', ctypes.c_int, [ctypes.POINTER(LatentMapperParams), c_vp]),
     ('sg3_clip_preprocess', ctypes.c_int, [ctypes.POINTER(ClipPreprocessParams), c_vp]),
+    ('sg3_clip_supported', ctypes.c_int, [ctypes.c_int] * 3),
+    ('sg3_clip_layernorm', ctypes.c_int, [ctypes.POINTER(ClipLayernormParams), c_vp]),
+    ('sg3_clip_gemm', ctypes.c_int, [ctypes.POINTER(ClipGemmParams), c_vp]),
+    ('sg3_clip_attention', ctypes.c_int, [ctypes.POINTER(ClipAttentionParams), c_vp]),
+    ('sg3_clip_embed', ctypes.c_int, [ctypes.POINTER(ClipEmbedParams), c_vp]),
 ]
 
 _lib = None

@@ -1,5 +1,6 @@
 """Time the StyleCLIP delta_i_c sweep on seeded T-1024 / R-1024 weights with the stand-in image encoder of the tests
-(tests/delta_i_c_cases.py; the CLIP model is external, so its share here is the stand-in's, not ViT-B/32's).
+(tests/delta_i_c_cases.py; its share is the stand-in's, not ViT-B/32's) or, with --encoder clip, with the package's own CLIP at
+the full ViT-B/32 size on seeded weights (tests/clip_cases.py 'b32'; the kernels' time does not depend on the weights' values).
 
 Per configuration and num_samples in {1, 8}: channels per second over a window of consecutive channels through
 `compute_clip_features` (host clock around work that ends in a device synchronise), and the split of device time between synthesis,
@@ -7,7 +8,7 @@ preprocessing and the encoder (device events around the three stages of the same
 against the torch composite at B in {1, 32} from 1024 x 1024, alternating the two in one timed loop.  From the measured rates the
 time of a full sweep at num_samples 1 and 300 is extrapolated (channels x 2 x num_samples images at the measured images per
 second) and labelled as such.  Prints one JSON line.
-    python tools/time_delta_i_c.py [--configs T1024 R1024] [--channels 128] [--reps 3]"""
+    python tools/time_delta_i_c.py [--configs T1024 R1024] [--channels 128] [--reps 3] [--encoder stand-in|clip]"""
 import argparse
 import json
 import os
@@ -77,17 +78,23 @@ def main():
     ap.add_argument('--channels', type=int, default=128, help='channels in the timed window at num_samples 1 (an eighth of it at 8)')
     ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--force-fp32', action='store_true')
+    ap.add_argument('--encoder', choices=['stand-in', 'clip'], default='stand-in', help="clip: the native ViT-B/32 (models/clip) on seeded weights")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('time_delta_i_c.py measures on a GPU; none is visible')
     from editing.styleclip_global_directions.preprocess.create_delta_i_c import _endpoints, compute_clip_features
     from editing.styleclip_global_directions.preprocess.s_statistics import compute_stats
     kw = dict(force_fp32=True) if a.force_fp32 else {}
-    res = {'box': torch.cuda.get_device_name(0), 'max_batch': MAX_BATCH, 'force_fp32': bool(a.force_fp32), 'encoder': 'stand-in (8x8 pool, 192x16 matrix)'}
+    res = {'box': torch.cuda.get_device_name(0), 'max_batch': MAX_BATCH, 'force_fp32': bool(a.force_fp32),
+           'encoder': 'stand-in (8x8 pool, 192x16 matrix)' if a.encoder == 'stand-in' else 'native ViT-B/32, 12 layers, seeded weights, HIP kernels'}
     for b in (1, 32):
         fused, comp = op_times(b)
         res[f'preprocess_b{b}_fused_us'], res[f'preprocess_b{b}_composite_us'] = fused, comp
-    encoder = cases.StandInEncoder()
+    if a.encoder == 'clip':
+        import clip_cases
+        encoder = clip_cases.build('b32', device=DEV).encode_image
+    else:
+        encoder = cases.StandInEncoder()
     for cfg in a.configs:
         G = build_product_generator(cfg, device=DEV)
         _, all_s, (_, mean, std) = compute_stats(G, random_state=3, num_images=64, batch=16)
