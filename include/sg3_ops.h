@@ -425,18 +425,58 @@ typedef struct sg3_modconv_params {
      * bytes and hand the [..., :outW] view on: a 1046-float row is 4184 bytes, so every 128-byte store segment of a dense output
      * straddles two cache lines (3x3 split-precision / fp16 kernels only; other forms require 0 or outW). */
     int32_t        outRowStride;
-    /* Optional scratch for small grids (batch 1 on the 36^2 .. 84^2 maps: fewer tiles than CUs): the 3x3 direct kernel and the 1x1
+    /* Optional scratch for small grids (batch 1 on the 36^2 .. 84^2 maps: fewer tiles than CUs): the flat 3x3 direct kernel and the 1x1
      * GEMM kernel (fp32 tensors) then split the input channels of a tile over up to four workgroups and a second launch adds their
-     * partial sums in order.  NULL / too
-     * small = no split (same result up to fp32 summation order).  sg3_modconv_split_scratch_floats gives a sufficient size. */
+     * partial sums in order.  A call splits only when ALL of this holds (sg3_modconv_dispatch reports the outcome as kSplits):
+     *   3x3: dcoef present, outW <= 128, ceil(I/16) >= 8 and N * ceil(O/64) * ceil(outH*outW/128) (the workgroups of the smallest
+     *        flat tile) below the CU count;
+     *   1x1: fp32 tensors, pad 0, O > 4, ceil(I/32) >= 8 and 4 * N * ceil(O/256) * ceil(H*W/256) below the CU count;
+     *   (SG3_FLAT_SPLITS >= 2 in the environment stands in for the channel and workgroup counts, A/B timing)
+     * and the chosen kernel's own grid leaves CUs idle, and the scratch holds kSplits partial images.  NULL / too small = no split
+     * (same result up to fp32 summation order).  sg3_modconv_split_scratch_floats gives the exact size. */
     float*         splitScratch;
     int64_t        splitScratchFloats;
 } sg3_modconv_params;
 
 SG3_API int sg3_modulated_conv2d(const sg3_modconv_params* p, void* stream);
 
-/* floats of splitScratch that let this call split its K loop (0 = the call would not split) */
+/* floats of splitScratch with which this call splits its K loop: kSplits * N * O * outH * outW of the plan made as if scratch were
+ * unlimited (0 = the call would not split) */
 SG3_API int64_t sg3_modconv_split_scratch_floats(const sg3_modconv_params* p);
+
+/* kernel families of sg3_modulated_conv2d */
+enum {
+    SG3_MODCONV_NONE      = -1, /* no launch: the grid would pass 2^31 - 1 workgroups */
+    SG3_MODCONV_FP32_MFMA = 0,  /* modconv_mfma_kernel<T, k, WM, WN, TM, TN>: exact fp32 products */
+    SG3_MODCONV_TORGB     = 1,  /* modconv_1x1_small_kernel: 1x1, O <= 4 */
+    SG3_MODCONV_ROWS      = 2,  /* modconv_f16x3_kernel<T, WM, WN, TN, SPLIT, PACK>: 3x3, 32 WM channels x (WN TN rows x 32 columns) */
+    SG3_MODCONV_FLAT      = 3,  /* modconv_flat_kernel<T, TN, SPLIT>: 3x3 on narrow planes, 64 channels x runs of 64 TN pixels */
+    SG3_MODCONV_GEMM1     = 4,  /* modconv1_f16x3_kernel<T, WM, WN, TM, TN, SPLIT, NBUF, M16>: 1x1, 32 WM TM channels x 256 pixels */
+    SG3_MODCONV_F23       = 5,  /* modconv_f23_kernel<TN, T>: 3x3 in the transform domain, TN rows per wave */
+};
+
+/* What sg3_modulated_conv2d launches for a call: kernel family, template coordinates (0 where the family has none), launch geometry. */
+typedef struct sg3_modconv_dispatch_info {
+    int32_t        family;     /* SG3_MODCONV_* */
+    int32_t        WM, WN, TM, TN;
+    int32_t        SPLIT;      /* fp16 hi/lo operands (three MFMAs per product) */
+    int32_t        PACK;       /* ROWS: tap-packed last K chunk */
+    int32_t        NBUF;       /* GEMM1: LDS images (1 = two workgroups per CU) */
+    int32_t        M16;        /* GEMM1: the 16x16x32 MFMA form */
+    int32_t        nch;        /* K chunks (GEMM1: stages of 32 channels) */
+    int32_t        xTiles, yTiles, mTiles;
+    int32_t        kSplits;    /* workgroups sharing a tile's input channels; > 1: a reduce launch follows */
+    int32_t        totalBlocks; /* tiles x kSplits the grid walks (F23: persistent workgroups, gridX = min(totalBlocks, CUs)) */
+    int32_t        gridX, gridY, block;
+    int32_t        ldsBytes;   /* dynamic LDS of the launch */
+    int32_t        outPitch;   /* elements between output rows */
+    int32_t        reduceGrid; /* workgroups (of 256) of modconv_split_reduce_kernel, 0 without a split */
+} sg3_modconv_dispatch_info;
+
+/* The plan of a call, from the function the launch itself uses (host only: no launch, no pointer followed -- only whether dcoef,
+ * epilogueBias and splitScratch are set is read, so placeholders do; x, wPacked, sIn and out may be NULL).  `cus` <= 0: the CU count
+ * of the current device, 256 without one.  SG3_BAD_ARG for a call sg3_modulated_conv2d rejects. */
+SG3_API int sg3_modconv_dispatch(const sg3_modconv_params* p, int cus, sg3_modconv_dispatch_info* out);
 
 /* ------------------------------------------------------------------------
  * conv2d_wgrad -- per-sample weight gradient of the (modulated) convolution, the part of the backward of

@@ -7,7 +7,7 @@
 //
 // so all samples share one weight matrix:  M = O (out channels), N = pixels, K = I*k*k.
 //
-// Kernels in this file (the host picks one per call, see sg3_modulated_conv2d):
+// Kernels in this file (plan_modconv in sg3_modconv_plan.h picks one per call; sg3_modulated_conv2d launches the plan):
 //   * modconv_f16x3_kernel   3x3, split precision (fp16 hi/lo operands, three fp16 MFMAs per product, fp32-equivalent) or
 //                            plain fp16 (the reference's mixed-precision layers): the default when |x| is bounded;
 //   * modconv1_f16x3_kernel  1x1 (config R), same arithmetic, a plain GEMM over flat 256-pixel tiles;
@@ -29,22 +29,12 @@
 #include <algorithm>
 #include <cstdlib>
 
-#ifndef SG3_TAILPACK
-#define SG3_TAILPACK 1          // 0 compiles the tap-packed tail chunk of the 3x3 kernel out (A/B builds)
-#endif
-
 namespace sg3 {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-template <int KS> struct ConvK;
-template <> struct ConvK<3> { static constexpr int TAPS = 9, KC = 8; };
-template <> struct ConvK<1> { static constexpr int TAPS = 1, KC = 16; };
-
-static inline int packed_kc(int k) { return k == 3 ? ConvK<3>::KC : ConvK<1>::KC; }
-// 16-channel chunks of the f16x3 packing; 1x1 kernels stage two chunks per step, so their count is padded to even
-static inline int f16x3_chunks(int I, int k) { const int c = (I + 15) / 16; return k == 1 ? (c + 1) / 2 * 2 : c; }
+// ConvK, packed_kc, f16x3_chunks and FLAT_NPIX: sg3_modconv_plan.h (packing and tile constants the plan shares with the kernels)
 
 struct ConvParams {
     const void* x; const float* wp; const float* sIn; const float* dcoef; void* out;
@@ -511,7 +501,6 @@ modconv_f16x3_kernel(ConvParams p) {
 // row those runs touch (+ 2), full width (+ 2): at most FLAT_NPIX pixels.  Every lane keeps the patch offset of its pixel for
 // each of its TN runs; a tap adds (ky PW + kx).  No row streaming (a run's neighbours in y are not a run): tap by tap, the A
 // fragments of a tap held over the TN runs.  Same packed weights, style / demodulation handling and arithmetic as the row kernel.
-constexpr int FLAT_NPIX = 512;                 // patch pixels staged per chunk (two per thread)
 
 template <typename T, int TN, bool SPLIT>
 __global__ void __launch_bounds__(256, 2)
@@ -1101,25 +1090,6 @@ modconv_1x1_small_kernel(ConvParams p, int vec) {
     }
 }
 
-template <typename T>
-static int launch_conv_1x1_small(const sg3_modconv_params& q, hipStream_t st) {
-    ConvParams p;
-    p.x = q.x; p.wp = q.wPacked; p.sIn = q.sIn; p.dcoef = q.dcoef; p.out = q.out;
-    p.N = q.N; p.I = q.I; p.O = q.O; p.H = q.H; p.W = q.W; p.pad = 0; p.outH = q.H; p.outW = q.W;
-    p.nch = ceil_div(q.I, ConvK<1>::KC);
-    p.xTiles = p.yTiles = p.mTiles = 1; p.totalBlocks = 0;
-    p.epBias = q.epilogueBias;
-    p.epClamp = q.epilogueClamp >= 0.f ? q.epilogueClamp : INFINITY;
-    p.epScale = q.epilogueScale != 0.f ? q.epilogueScale : 1.f;
-    const int HW = q.H * q.W;
-    const int vec = (HW % 4 == 0) && (((size_t)q.x | (size_t)q.out) % 16 == 0) ? 1 : 0;
-    int bx = ceil_div(vec ? HW / 4 : HW, 256);
-    if (bx > 2048) bx = 2048;
-    hipLaunchKernelGGL((modconv_1x1_small_kernel<T, 4>), dim3(bx, q.N), dim3(256), (size_t)q.I * 4 * sizeof(float), st, p, vec);
-    SG3_LAUNCH_CHECK("modconv_1x1_small_kernel");
-    return SG3_OK;
-}
-
 // ---------------------------------------------------------------------------
 // prep A: one workgroup per output channel: normalise the filter, pack it, and emit wsq[o][i] = sum_taps wn^2
 static __device__ __forceinline__ void prep_w_body(const sg3_modconv_prep_params& p, int kc, int nch, int o, float* red) {
@@ -1258,72 +1228,6 @@ modconv_prep_s_batch_kernel(PrepBatch b) {
     prep_s_body(b.p[l], local / gy, local % gy, gy, red, s2);
 }
 
-template <typename T, int KS, int WM, int WN, int TM, int TN>
-static int launch_conv(const sg3_modconv_params& q, hipStream_t st) {
-    constexpr int BM = WM * TM * 32, ROWS = WN * TN;
-    ConvParams p;
-    p.x = q.x; p.wp = q.wPacked; p.sIn = q.sIn; p.dcoef = q.dcoef; p.out = q.out;
-    p.N = q.N; p.I = q.I; p.O = q.O; p.H = q.H; p.W = q.W; p.pad = q.pad;
-    p.outH = q.H + 2 * q.pad - KS + 1; p.outW = q.W + 2 * q.pad - KS + 1;
-    p.nch = ceil_div(q.I, ConvK<KS>::KC);
-    p.xTiles = ceil_div(p.outW, 32); p.yTiles = ceil_div(p.outH, ROWS); p.mTiles = ceil_div(q.O, BM);
-    const long long total = (long long)p.xTiles * p.yTiles * p.mTiles * q.N;
-    if (total > 0x7fffffffLL) { set_error("modulated_conv2d: grid too large"); return SG3_BAD_ARG; }
-    p.totalBlocks = (int)total;
-    hipLaunchKernelGGL((modconv_mfma_kernel<T, KS, WM, WN, TM, TN>), dim3((unsigned)total), dim3(256), 0, st, p);
-    SG3_LAUNCH_CHECK("modconv_mfma_kernel");
-    return SG3_OK;
-}
-
-template <typename T, int KS>
-static int dispatch_conv(const sg3_modconv_params& q, hipStream_t st) {
-    // M tile from the channel count: the smallest BM in {32,64,96,128} that wastes the least of the last tile
-    const int O = q.O;
-    int best = 128; double bestEff = 0.0;
-    const int cands[4] = {128, 96, 64, 32};
-    for (int c = 0; c < 4; c++) {
-        const int bm = cands[c];
-        const double eff = (double)O / (double)(ceil_div(O, bm) * bm);
-        if (eff > bestEff + 1e-9) { bestEff = eff; best = bm; }
-    }
-    switch (best) {
-        case 128: return launch_conv<T, KS, 2, 2, 2, 2>(q, st);
-        case 96:  return launch_conv<T, KS, 1, 4, 3, 1>(q, st);
-        case 64:  return launch_conv<T, KS, 1, 4, 2, 2>(q, st);
-        default:  return launch_conv<T, KS, 1, 4, 1, 4>(q, st);
-    }
-}
-
-template <typename T, int WM, int WN, int TN, bool SPLIT, bool PACK>
-static int launch_conv_f16x3(const sg3_modconv_params& q, hipStream_t st) {
-    constexpr int BM = WM * 32, ROWS = WN * TN;
-    constexpr int PH = ROWS + 2, PW = 34;
-    constexpr size_t ldsBytes = ((size_t)BM * (9 * 32 + 8) + (SPLIT ? 4 : 2) * (size_t)PH * PW * 8) * sizeof(_Float16);
-    ConvParams p;
-    p.x = q.x; p.wp = q.wPacked; p.sIn = q.sIn; p.dcoef = q.dcoef; p.out = q.out;
-    p.N = q.N; p.I = q.I; p.O = q.O; p.H = q.H; p.W = q.W; p.pad = q.pad;
-    p.outH = q.H + 2 * q.pad - 2; p.outW = q.W + 2 * q.pad - 2;
-    p.nch = ceil_div(q.I, 16);
-    p.xTiles = ceil_div(p.outW, 32); p.yTiles = ceil_div(p.outH, ROWS); p.mTiles = ceil_div(q.O, BM);
-    const long long total = (long long)p.xTiles * p.yTiles * p.mTiles * q.N;
-    if (total > 0x7fffffffLL) { set_error("modulated_conv2d: grid too large"); return SG3_BAD_ARG; }
-    p.totalBlocks = (int)total;
-    p.outPitch = q.outRowStride > 0 ? q.outRowStride : p.outW;
-    p.tailPack = PACK ? 1 : 0;
-    auto kern = modconv_f16x3_kernel<T, WM, WN, TN, SPLIT, PACK>;
-    if (ldsBytes > 64 * 1024)
-        SG3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes));
-    hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(256), ldsBytes, st, p);
-    SG3_LAUNCH_CHECK("modconv_f16x3_kernel");
-    return SG3_OK;
-}
-
-// SG3_CONV3_ROWS=1 in the environment keeps the narrow 3x3 layers on the row-tile kernel (A/B timing; read once)
-static bool conv3_use_flat() {
-    static const bool v = [] { const char* e = getenv("SG3_CONV3_ROWS"); return !(e && e[0] == '1'); }();
-    return v;
-}
-
 // out[n][o][f] = d[n][o] * sum_ks partial[ks][n][o][f] (ks in order: reproducible; d = 1 when dcoef is null: the 1x1 kernel applies it
 // before storing its partial image), the second half of a K-split convolution
 template <typename T>
@@ -1337,186 +1241,132 @@ modconv_split_reduce_kernel(const float* __restrict__ partial, const float* __re
     }
 }
 
-// CUs of the current device, read once per device
-static int conv_cu_count() {
-    static int cus[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (cus[dev] == 0) {
-        int n = 0;
-        cus[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
+// ---------------------------------------------------------------------------
+// Launch side: the plan (sg3_modconv_plan.h) names the kernel and its geometry; here it is turned into the template instantiation.
+
+template <typename T, int KS>
+static int launch_mfma(const ConvParams& p, const ConvPlan& pl, hipStream_t st) {
+    auto go = [&](auto kern) { return launch_kernel(kern, "modconv_mfma_kernel", pl, st, p); };
+    switch (pl.WM * pl.TM * 32) {
+        case 128: return go(modconv_mfma_kernel<T, KS, 2, 2, 2, 2>);
+        case 96:  return go(modconv_mfma_kernel<T, KS, 1, 4, 3, 1>);
+        case 64:  return go(modconv_mfma_kernel<T, KS, 1, 4, 2, 2>);
+        default:  return go(modconv_mfma_kernel<T, KS, 1, 4, 1, 4>);
     }
-    return cus[dev];
 }
 
-// K splits of a flat-kernel call with `tiles` workgroups and `nch` K chunks: none when the grid gives every CU a workgroup; else up to
-// four, at least four chunks each
-static int flat_forced_splits() {
-    static const int forced = [] { const char* e = getenv("SG3_FLAT_SPLITS"); return e ? atoi(e) : 0; }();      // A/B timing: 1 = never split, 2 .. 4 = always
-    return forced;
-}
-static int flat_k_splits(long long tiles, int nch) {
-    const int forced = flat_forced_splits();
-    if (forced >= 1) return std::min(forced, std::min(4, nch));
-    const int cus = conv_cu_count();
-    if (tiles >= cus) return 1;
-    const int s = (int)std::min<long long>(std::min<long long>(4, (2LL * cus) / tiles), nch / 4);
-    return s >= 2 ? s : 1;
-}
-
-// does the patch of every RUN-pixel piece of an outH x outW plane fit FLAT_NPIX pixels?  rows touched <= (RUN - 2) / outW + 2
-static bool flat_fits(int outW, int run) { return ((run - 2) / outW + 2 + 2) * (outW + 2) <= FLAT_NPIX; }
-
-template <typename T, int TN, bool SPLIT>
-static int launch_conv_flat(const sg3_modconv_params& q, hipStream_t st) {
-    constexpr int RUN = 2 * TN * 32;
-    constexpr size_t ldsBytes = ((size_t)64 * (9 * 32 + 8) + (SPLIT ? 4 : 2) * (size_t)FLAT_NPIX * 8) * sizeof(_Float16);
-    static_assert(ldsBytes <= 80 * 1024, "two workgroups per CU");
-    ConvParams p;
-    p.x = q.x; p.wp = q.wPacked; p.sIn = q.sIn; p.dcoef = q.dcoef; p.out = q.out;
-    p.N = q.N; p.I = q.I; p.O = q.O; p.H = q.H; p.W = q.W; p.pad = q.pad;
-    p.outH = q.H + 2 * q.pad - 2; p.outW = q.W + 2 * q.pad - 2;
-    p.nch = ceil_div(q.I, 16);
-    p.xTiles = ceil_div(p.outH * p.outW, RUN); p.yTiles = 1; p.mTiles = ceil_div(q.O, 64);
-    const long long total = (long long)p.xTiles * p.mTiles * q.N;
-    if (total > 0x7fffffffLL) { set_error("modulated_conv2d: grid too large"); return SG3_BAD_ARG; }
-    p.outPitch = p.outW; p.tailPack = 0;
-    p.kSplits = 1; p.partial = nullptr;
-    const long long planes = (long long)q.N * q.O, P = (long long)p.outH * p.outW;
-    if (q.splitScratch && q.dcoef) {
-        const int ksp = flat_k_splits(total, p.nch);
-        if (ksp > 1 && (long long)ksp * planes * P <= q.splitScratchFloats && (long long)ksp * total <= 0x7fffffffLL) { p.kSplits = ksp; p.partial = q.splitScratch; }
-    }
-    p.totalBlocks = (int)(total * p.kSplits);
-    auto kern = modconv_flat_kernel<T, TN, SPLIT>;
-    if (ldsBytes > 64 * 1024)
-        SG3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes));
-    hipLaunchKernelGGL(kern, dim3((unsigned)p.totalBlocks), dim3(256), ldsBytes, st, p);
-    SG3_LAUNCH_CHECK("modconv_flat_kernel");
-    if (p.kSplits > 1) {
-        const long long elems = planes * P;
-        const unsigned blocks = (unsigned)std::min<long long>((elems + 255) / 256, 4096);
-        hipLaunchKernelGGL((modconv_split_reduce_kernel<T>), dim3(blocks), dim3(256), 0, st, (const float*)p.partial, q.dcoef, (T*)q.out, p.kSplits, planes, (int)P);
-        SG3_LAUNCH_CHECK("modconv_split_reduce_kernel");
-    }
-    return SG3_OK;
+template <typename T>
+static int launch_torgb(ConvParams& p, const sg3_modconv_params& q, ConvPlan pl, hipStream_t st) {
+    p.epBias = q.epilogueBias;
+    p.epClamp = q.epilogueClamp >= 0.f ? q.epilogueClamp : INFINITY;
+    p.epScale = q.epilogueScale != 0.f ? q.epilogueScale : 1.f;
+    const int HW = q.H * q.W;
+    const int vec = (HW % 4 == 0) && (((size_t)q.x | (size_t)q.out) % 16 == 0) ? 1 : 0;
+    if (!vec) pl.gridX = torgb_blocks(HW, false);          // the plan counts on four pixels per thread whenever the plane allows
+    return launch_kernel(modconv_1x1_small_kernel<T, 4>, "modconv_1x1_small_kernel", pl, st, p, vec);
 }
 
 template <typename T, bool SPLIT>
-static int dispatch_conv_f16x3(const sg3_modconv_params& q, hipStream_t st) {
-    // Two row-streaming tiles, two workgroups per CU each.  The 64-channel tile stages the patch once for twice the
-    // channels; the 32-channel tile pads the channel count less.  Measured at FFHQ-1024 (batch 8): O = 81 (96 vs 128
-    // padded rows) 1.76 vs 2.10 ms, O = 203 (224 vs 256) 2.40 vs 2.54 ms, O = 323 (352 vs 384) 1.86 vs 1.77 ms: the
-    // small tile wins when it saves at least ~10 % of the rows.
-    const int O = q.O;
-    const int t32 = ceil_div(O, 32) * 32, t64 = ceil_div(O, 64) * 64;
-    // last K chunk with 1..4 channels (and at least one full chunk before it): the kernel packs its taps (PACK)
-    const bool pack = SG3_TAILPACK && q.I > 16 && q.I % 16 >= 1 && q.I % 16 <= 4;
-    // The plain fp16 form (one MFMA per K step) reads 0.75 LDS fragments per MFMA with four rows per wave -- LDS-bandwidth bound,
-    // where the split form (0.5 per MFMA, three MFMAs per fragment pair) is not: its waves take taller stacks of rows (six: 0.61; five in the 32-channel tile: 0.67; eight rows spill).
-    // SG3_CONV_F16_ROWS4=1 keeps four rows (A/B timing).
-    static const bool tallF16 = [] { const char* e = getenv("SG3_CONV_F16_ROWS4"); return !(e && e[0] == '1'); }();
-    const bool tall = !SPLIT && tallF16 && q.H + 2 * q.pad - 2 >= 128;
-    if (O <= 32 || t32 * 10 <= t64 * 9) {                                                          //  32 x (16 rows x 32)
-        if constexpr (!SPLIT) {
-            if (tall) return pack ? launch_conv_f16x3<T, 1, 4, 5, SPLIT, true>(q, st) : launch_conv_f16x3<T, 1, 4, 5, SPLIT, false>(q, st);
+static int launch_rows(const ConvParams& p, const ConvPlan& pl, hipStream_t st) {
+    auto go = [&](auto kern) { return launch_kernel(kern, "modconv_f16x3_kernel", pl, st, p); };
+    const int key = pl.WM * 100 + pl.TN * 10 + pl.PACK;           // WN = 4 / WM
+    if constexpr (!SPLIT) {                                       // the tall stacks of the plain fp16 form
+        switch (key) {
+            case 150: return go(modconv_f16x3_kernel<T, 1, 4, 5, SPLIT, false>);
+            case 151: return go(modconv_f16x3_kernel<T, 1, 4, 5, SPLIT, true>);
+            case 260: return go(modconv_f16x3_kernel<T, 2, 2, 6, SPLIT, false>);
+            case 261: return go(modconv_f16x3_kernel<T, 2, 2, 6, SPLIT, true>);
         }
-        return pack ? launch_conv_f16x3<T, 1, 4, 4, SPLIT, true>(q, st) : launch_conv_f16x3<T, 1, 4, 4, SPLIT, false>(q, st);
     }
-    if constexpr (!SPLIT) {
-        if (tall) return pack ? launch_conv_f16x3<T, 2, 2, 6, SPLIT, true>(q, st) : launch_conv_f16x3<T, 2, 2, 6, SPLIT, false>(q, st);
+    switch (key) {
+        case 140: return go(modconv_f16x3_kernel<T, 1, 4, 4, SPLIT, false>);
+        case 141: return go(modconv_f16x3_kernel<T, 1, 4, 4, SPLIT, true>);
+        case 250: return go(modconv_f16x3_kernel<T, 2, 2, 5, SPLIT, false>);
+        case 240: return go(modconv_f16x3_kernel<T, 2, 2, 4, SPLIT, false>);
+        case 241: return go(modconv_f16x3_kernel<T, 2, 2, 4, SPLIT, true>);
     }
-    // Narrow outputs with 64-channel tiles: runs of the flattened plane instead of 32-column row pieces (modconv_flat_kernel) when
-    // that takes fewer rounds x MFMA blocks per wave than the best row tile.  SG3_CONV3_ROWS=1 keeps the row kernel.
-    if (!pack && (q.outRowStride == 0 || q.outRowStride == q.W + 2 * q.pad - 2) && conv3_use_flat()) {
-        const int outH = q.H + 2 * q.pad - 2, outW = q.W + 2 * q.pad - 2;
-        const long long perM = (long long)q.N * ceil_div(O, 64);
-        // time ~ rounds of 512 resident workgroups x (blocks per wave + staging); large grids are not quantised
-        auto cost = [](long long wgs, int tn) { return (wgs <= 2048 ? (double)ceil_div64(wgs, 512) : wgs / 512.0) * (tn + 0.5); };
-        const long long perRow = perM * ceil_div(outW, 32);
-        const double rowCost = std::min(cost(perRow * ceil_div(outH, 8), 4), cost(perRow * ceil_div(outH, 10), 5));
-        int best = 0; double bestCost = rowCost * 0.9;                       // the row kernel reads less LDS per MFMA: flat must save 10 %
-        for (int tn = 4; tn >= 2; tn--) {
-            if (!flat_fits(outW, 64 * tn)) continue;
-            const double c = cost(perM * ceil_div(outH * outW, 64 * tn), tn);
-            if (c < bestCost) { bestCost = c; best = tn; }
-        }
-        if (best == 4) return launch_conv_flat<T, 4, SPLIT>(q, st);
-        if (best == 3) return launch_conv_flat<T, 3, SPLIT>(q, st);
-        if (best == 2) return launch_conv_flat<T, 2, SPLIT>(q, st);
-    }
-    if (!pack) {
-        // Small grids (the 36^2 .. 52^2 layers): 512 workgroups are resident at once, so the time goes with the number of
-        // ROUNDS times the rows a workgroup computes.  Ten-row tiles turn the 640 workgroups of a 38-row output (8 images
-        // x 8 channel tiles x 2 x 5) into exactly 512: one round of 5 rows per wave instead of two rounds of 4.
-        const int outH = q.H + 2 * q.pad - 2, outW = q.W + 2 * q.pad - 2;
-        const long long per = (long long)q.N * ceil_div(O, 64) * ceil_div(outW, 32);
-        const long long wg8 = per * ceil_div(outH, 8), wg10 = per * ceil_div(outH, 10);
-        if (wg8 <= 2048 && ceil_div64(wg10, 512) * 5 < ceil_div64(wg8, 512) * 4)
-            return launch_conv_f16x3<T, 2, 2, 5, SPLIT, false>(q, st);                             //  64 x (10 rows x 32)
-    }
-    return pack ? launch_conv_f16x3<T, 2, 2, 4, SPLIT, true>(q, st) : launch_conv_f16x3<T, 2, 2, 4, SPLIT, false>(q, st);   //  64 x (8 rows x 32)
-}
-
-// SG3_CONV1_MFMA32=1 in the environment selects the 32x32x16 form of the 1x1 kernels (A/B timing; read once)
-static bool conv1_use_m16() {
-    static const bool v = [] { const char* e = getenv("SG3_CONV1_MFMA32"); return !(e && e[0] == '1'); }();
-    return v;
-}
-
-template <typename T, int WM, int WN, int TM, int TN, bool SPLIT, int NBUF = 2>
-static int launch_conv1_f16x3(const sg3_modconv_params& q, hipStream_t st) {
-    constexpr int BM = WM * TM * 32, ROWS = WN * TN;
-    constexpr size_t ldsBytes = NBUF * ((size_t)BM * (2 * 32 + 8) + (SPLIT ? 8 : 4) * (size_t)ROWS * 32 * 8) * sizeof(_Float16);
-    ConvParams p;
-    p.x = q.x; p.wp = q.wPacked; p.sIn = q.sIn; p.dcoef = q.dcoef; p.out = q.out;
-    p.N = q.N; p.I = q.I; p.O = q.O; p.H = q.H; p.W = q.W; p.pad = 0;
-    p.outH = q.H; p.outW = q.W;
-    p.nch = f16x3_chunks(q.I, 1) / 2;                  // stages of 32 channels
-    p.xTiles = ceil_div(q.H * q.W, ROWS * 32); p.yTiles = 1; p.mTiles = ceil_div(q.O, BM);     // flat 256-pixel tiles
-    const long long total = (long long)p.xTiles * p.yTiles * p.mTiles * q.N;
-    if (total > 0x7fffffffLL) { set_error("modulated_conv2d: grid too large"); return SG3_BAD_ARG; }
-    p.kSplits = 1; p.partial = nullptr;
-    if (q.splitScratch && std::is_same<T, float>::value) {
-        // this kernel's workgroups are eight waves with two resident per CU: measured neutral from ~100 tiles up (R-1024 batch 4: 15.1 vs
-        // 15.0 ms), +1.7 % at 48, +5.6 % at 24 -- so it splits below a quarter of a tile per CU
-        const int ksp = flat_k_splits(4 * total, p.nch);
-        const long long elems = (long long)q.N * q.O * q.H * q.W;
-        if (ksp > 1 && (long long)ksp * elems <= q.splitScratchFloats && (long long)ksp * total <= 0x7fffffffLL) { p.kSplits = ksp; p.partial = q.splitScratch; }
-    }
-    p.totalBlocks = (int)(total * p.kSplits);
-    // the 16x16x32 form for the compute-bound tiles (R-1024, batch 8: 28.4 vs 32.2 ms over the 1024 .. 406-channel layers); the
-    // thin HBM-bound layers keep 32x32x16: its stores are 128-byte row segments, the 16-wide blocks' 64-byte ones cost them 5 %
-    const bool m16 = NBUF == 2 && conv1_use_m16();
-    auto kern = m16 ? modconv1_f16x3_kernel<T, WM, WN, TM, TN, SPLIT, NBUF, true> : modconv1_f16x3_kernel<T, WM, WN, TM, TN, SPLIT, NBUF, false>;
-    if (ldsBytes > 64 * 1024)
-        SG3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes));
-    hipLaunchKernelGGL(kern, dim3((unsigned)p.totalBlocks), dim3(512), ldsBytes, st, p);
-    SG3_LAUNCH_CHECK("modconv1_f16x3_kernel");
-    if (p.kSplits > 1) {
-        const long long planes = (long long)q.N * q.O, P = (long long)q.H * q.W, elems = planes * P;
-        const unsigned blocks = (unsigned)std::min<long long>((elems + 255) / 256, 4096);
-        hipLaunchKernelGGL((modconv_split_reduce_kernel<T>), dim3(blocks), dim3(256), 0, st, (const float*)p.partial, (const float*)nullptr, (T*)q.out, p.kSplits, planes, (int)P);
-        SG3_LAUNCH_CHECK("modconv_split_reduce_kernel");
-    }
-    return SG3_OK;
+    set_error("modulated_conv2d: no row-tile kernel %d x %d rows, pack %d", pl.WM * 32, pl.WN * pl.TN, pl.PACK);
+    return SG3_BAD_ARG;
 }
 
 template <typename T, bool SPLIT>
-static int dispatch_conv1_f16x3(const sg3_modconv_params& q, hipStream_t st) {
-    // every staged input element is used once per output-channel tile, so the tile is as tall as the channel padding
-    // allows: 256 rows (1024 -> 1024 @ 148^2 x 4: 0.88 ms against 1.05 ms with 128 rows and 1.25 ms with 64)
-    // Few K stages (I <= 256: the 532^2 and 1044^2 layers of config R): HBM-bound, and ONE resident workgroup (100 KB of
-    // double-buffered LDS) leaves the CU waiting on memory at the start and end of every tile.  These layers take the
-    // 64-row tile with a single LDS image (42 KB, 110 registers): two workgroups per CU.  Measured at R-1024, batch 8:
-    // L10 256->161 1232 -> 1099 us, L11 161->102 2600 -> 2358, L12 102->64 1373 -> 1103, L13 64->64 945 -> 808 (5.5 TB/s).
-    // The 128-row tile needs 174 registers and spills under the two-workgroup bound.
-    const bool thin = q.I <= 256;
-    if (thin) return launch_conv1_f16x3<T, 1, 8, 2, 1, SPLIT, 1>(q, st);           //  64 x 256 pixels, two workgroups per CU
-    if (q.O <= 64) return launch_conv1_f16x3<T, 1, 8, 2, 1, SPLIT>(q, st);         //  64 x 256 pixels
-    const int t128 = ceil_div(q.O, 128) * 128, t256 = ceil_div(q.O, 256) * 256;
-    if (t256 <= t128) return launch_conv1_f16x3<T, 2, 4, 4, 2, SPLIT>(q, st);     // 256 x 256 pixels
-    return launch_conv1_f16x3<T, 2, 4, 2, 2, SPLIT>(q, st);                       // 128 x 256 pixels
+static int launch_flat(const ConvParams& p, const ConvPlan& pl, hipStream_t st) {
+    auto go = [&](auto kern) { return launch_kernel(kern, "modconv_flat_kernel", pl, st, p); };
+    switch (pl.TN) {
+        case 4:  return go(modconv_flat_kernel<T, 4, SPLIT>);
+        case 3:  return go(modconv_flat_kernel<T, 3, SPLIT>);
+        default: return go(modconv_flat_kernel<T, 2, SPLIT>);
+    }
+}
+
+template <typename T, bool SPLIT>
+static int launch_gemm1(const ConvParams& p, const ConvPlan& pl, hipStream_t st) {
+    auto go = [&](auto m16, auto m32) { return launch_kernel(pl.M16 ? m16 : m32, "modconv1_f16x3_kernel", pl, st, p); };
+    if (pl.NBUF == 1) return go(modconv1_f16x3_kernel<T, 1, 8, 2, 1, SPLIT, 1, true>, modconv1_f16x3_kernel<T, 1, 8, 2, 1, SPLIT, 1, false>);
+    switch (pl.WM * pl.TM * 32) {
+        case 256: return go(modconv1_f16x3_kernel<T, 2, 4, 4, 2, SPLIT, 2, true>, modconv1_f16x3_kernel<T, 2, 4, 4, 2, SPLIT, 2, false>);
+        case 128: return go(modconv1_f16x3_kernel<T, 2, 4, 2, 2, SPLIT, 2, true>, modconv1_f16x3_kernel<T, 2, 4, 2, 2, SPLIT, 2, false>);
+        default:  return go(modconv1_f16x3_kernel<T, 1, 8, 2, 1, SPLIT, 2, true>, modconv1_f16x3_kernel<T, 1, 8, 2, 1, SPLIT, 2, false>);
+    }
+}
+
+template <typename T>
+static int launch_plan(const sg3_modconv_params& q, const ConvPlan& pl, hipStream_t st) {
+    ConvParams p;
+    fill_params(p, q, pl);
+    p.tailPack = pl.PACK;
+    p.epBias = nullptr; p.epClamp = 0.f; p.epScale = 1.f;
+    p.kSplits = pl.kSplits; p.partial = pl.kSplits > 1 ? q.splitScratch : nullptr;
+    int rc = SG3_BAD_ARG;
+    switch (pl.family) {
+        case SG3_MODCONV_FP32_MFMA: rc = q.k == 3 ? launch_mfma<T, 3>(p, pl, st) : launch_mfma<T, 1>(p, pl, st); break;
+        case SG3_MODCONV_TORGB:     rc = launch_torgb<T>(p, q, pl, st); break;
+        case SG3_MODCONV_ROWS:      rc = pl.SPLIT ? launch_rows<T, true>(p, pl, st) : launch_rows<T, false>(p, pl, st); break;
+        case SG3_MODCONV_FLAT:      rc = pl.SPLIT ? launch_flat<T, true>(p, pl, st) : launch_flat<T, false>(p, pl, st); break;
+        case SG3_MODCONV_GEMM1:     rc = pl.SPLIT ? launch_gemm1<T, true>(p, pl, st) : launch_gemm1<T, false>(p, pl, st); break;
+        default: set_error("modulated_conv2d: grid too large"); break;
+    }
+    if (rc != SG3_OK || pl.kSplits == 1) return rc;
+    // second half of a K-split convolution; the 1x1 kernel has applied dcoef before storing its partial image
+    const long long planes = (long long)q.N * q.O;
+    hipLaunchKernelGGL((modconv_split_reduce_kernel<T>), dim3(pl.reduceGrid), dim3(256), 0, st, (const float*)q.splitScratch,
+                       pl.family == SG3_MODCONV_FLAT ? q.dcoef : (const float*)nullptr, (T*)q.out, pl.kSplits, planes, p.outH * p.outW);
+    SG3_LAUNCH_CHECK("modconv_split_reduce_kernel");
+    return SG3_OK;
+}
+
+// what sg3_modulated_conv2d refuses, apart from missing tensors
+static int validate_call(const sg3_modconv_params* p) {
+    SG3_REQUIRE(p->N > 0 && p->I > 0 && p->O > 0 && p->H > 0 && p->W > 0, "modulated_conv2d: empty tensor");
+    SG3_REQUIRE(p->k == 1 || p->k == 3, "modulated_conv2d: kernel size must be 1 or 3");
+    SG3_REQUIRE(p->pad >= 0 && p->pad <= p->k - 1, "modulated_conv2d: padding must be in [0, k-1]");
+    SG3_REQUIRE(p->H + 2 * p->pad - p->k + 1 > 0 && p->W + 2 * p->pad - p->k + 1 > 0, "modulated_conv2d: empty output");
+    SG3_REQUIRE(p->dtype == SG3_F32 || p->dtype == SG3_F16, "modulated_conv2d: unsupported dtype");
+    const bool f23 = p->precision == SG3_CONV_F16X3_F23 || p->precision == SG3_CONV_F16_F23;
+    const bool f16 = p->precision == SG3_CONV_F16X3 || p->precision == SG3_CONV_F16;
+    {
+        const int outW = p->W + 2 * p->pad - p->k + 1;
+        const bool rowStream = p->k == 3 && (f16 || f23);
+        SG3_REQUIRE(p->outRowStride == 0 || p->outRowStride == outW || (rowStream && p->outRowStride > outW),
+                    "modulated_conv2d: outRowStride must be 0 or outW (a larger pitch is supported by the 3x3 f16x3 / f16 kernels only)");
+    }
+    const bool torgb = p->precision == SG3_CONV_FP32 && p->k == 1 && p->pad == 0 && p->O <= 4 && (size_t)p->I * 4 * sizeof(float) <= 48 * 1024;
+    SG3_REQUIRE(!p->epilogueBias || torgb, "modulated_conv2d: the bias / clamp / scale epilogue exists for the ToRGB kernel only (1x1, O <= 4, fp32 form)");
+    if (f23) {
+        SG3_REQUIRE(p->dcoef, "modulated_conv2d: the transform-domain forms need dcoef");
+        SG3_REQUIRE(p->dtype == (p->precision == SG3_CONV_F16X3_F23 ? SG3_F32 : SG3_F16),
+                    "modulated_conv2d: SG3_CONV_F16X3_F23 takes fp32 tensors, SG3_CONV_F16_F23 fp16 tensors");
+        SG3_REQUIRE(f23_supported(p->dtype, p->I, p->O, p->H, p->W, p->k, p->pad, p->outRowStride),
+                    "modulated_conv2d: the transform-domain forms take 3x3 kernels with even W, pad and row pitch (sg3_modconv_f23_supported)");
+    } else if (f16) {
+        SG3_REQUIRE(p->dcoef, "modulated_conv2d: f16x3 needs dcoef");
+        SG3_REQUIRE(p->k == 3 || p->pad == 0, "modulated_conv2d: f16x3 1x1 kernels take no padding");
+        SG3_REQUIRE(p->k == 3 || ((p->H * p->W) & 1) == 0, "modulated_conv2d: f16x3 1x1 kernels need an even number of pixels (pair loads)");
+        SG3_REQUIRE((int64_t)p->I * p->H * p->W * 4 < (int64_t)1 << 31, "modulated_conv2d: f16x3 needs a sample below 2 GiB (32-bit offsets)");
+    } else {
+        SG3_REQUIRE(p->precision == SG3_CONV_FP32, "modulated_conv2d: bad precision");
+    }
+    return SG3_OK;
 }
 
 } // namespace sg3
@@ -1553,23 +1403,23 @@ static int prep_validate(const sg3_modconv_prep_params* p) {
 
 int64_t sg3_modconv_split_scratch_floats(const sg3_modconv_params* p) {
     using namespace sg3;
-    // an upper bound for the one form that splits K over workgroups (3x3, split-precision / fp16 direct kernels on narrow maps with a
-    // grid smaller than the chip): 4 partial images; 0 when the call cannot take it
-    if (!p || (p->precision != SG3_CONV_F16X3 && p->precision != SG3_CONV_F16)) return 0;
-    if (p->k == 1) {
-        // the 1x1 GEMM kernel (config R): fp32 tensors, 256-pixel tiles x up to 256 rows; its stages are 32 channels
-        if (p->dtype != SG3_F32 || p->pad != 0 || p->O <= 4) return 0;
-        const long long P1 = (long long)p->H * p->W;
-        const long long tiles1 = (long long)p->N * ceil_div(p->O, 256) * ceil_div((int)std::min<long long>(P1, 0x7fffffff), 256);
-        if (flat_forced_splits() < 2 && (4 * tiles1 >= conv_cu_count() || ceil_div(p->I, 32) < 8)) return 0;
-        return 4LL * p->N * p->O * P1;
-    }
-    if (p->k != 3 || !p->dcoef) return 0;
-    const long long outH = p->H + 2 * p->pad - 2, outW = p->W + 2 * p->pad - 2;
-    if (outH <= 0 || outW <= 0 || outW > 128) return 0;
-    const long long tiles = (long long)p->N * ceil_div(p->O, 64) * ceil_div((int)(outH * outW), 128);      // the smallest flat tile
-    if (flat_forced_splits() < 2 && (tiles >= conv_cu_count() || ceil_div(p->I, 16) < 8)) return 0;
-    return 4LL * p->N * p->O * outH * outW;
+    // the plan of the call with unlimited scratch on offer: kSplits partial images where it splits K over workgroups, else 0
+    if (!p || validate_call(p) != SG3_OK) return 0;
+    sg3_modconv_params q = *p;
+    float anything;
+    q.splitScratch = &anything; q.splitScratchFloats = INT64_MAX;
+    const ConvPlan pl = plan_modconv(q, conv_cu_count(), ConvKnobs::env(), f23_forced_rows());
+    if (pl.family == SG3_MODCONV_NONE || pl.kSplits <= 1) return 0;
+    return (int64_t)pl.kSplits * p->N * p->O * (p->H + 2 * p->pad - p->k + 1) * (p->W + 2 * p->pad - p->k + 1);
+}
+
+int sg3_modconv_dispatch(const sg3_modconv_params* p, int cus, sg3_modconv_dispatch_info* out) {
+    using namespace sg3;
+    SG3_REQUIRE(p && out, "modconv_dispatch: null argument");
+    { const int rc = validate_call(p); if (rc != SG3_OK) return rc; }
+    *out = plan_modconv(*p, cus > 0 ? cus : conv_cu_count(), ConvKnobs::env(), f23_forced_rows());
+    SG3_REQUIRE(out->family != SG3_MODCONV_NONE, "modulated_conv2d: grid too large");
+    return SG3_OK;
 }
 
 int sg3_modconv_f23_supported(int dtype, int I, int O, int H, int W, int k, int pad, int outRowStride) {
@@ -1629,46 +1479,11 @@ int sg3_modulated_conv2d_prep(const sg3_modconv_prep_params* p, void* stream) {
 int sg3_modulated_conv2d(const sg3_modconv_params* p, void* stream) {
     using namespace sg3;
     SG3_REQUIRE(p && p->x && p->wPacked && p->sIn && p->out, "modulated_conv2d: null tensor");
-    SG3_REQUIRE(p->N > 0 && p->I > 0 && p->O > 0 && p->H > 0 && p->W > 0, "modulated_conv2d: empty tensor");
-    SG3_REQUIRE(p->k == 1 || p->k == 3, "modulated_conv2d: kernel size must be 1 or 3");
-    SG3_REQUIRE(p->pad >= 0 && p->pad <= p->k - 1, "modulated_conv2d: padding must be in [0, k-1]");
-    SG3_REQUIRE(p->H + 2 * p->pad - p->k + 1 > 0 && p->W + 2 * p->pad - p->k + 1 > 0, "modulated_conv2d: empty output");
-    SG3_REQUIRE(p->dtype == SG3_F32 || p->dtype == SG3_F16, "modulated_conv2d: unsupported dtype");
+    { const int rc = validate_call(p); if (rc != SG3_OK) return rc; }
+    const ConvPlan pl = plan_modconv(*p, conv_cu_count(), ConvKnobs::env(), f23_forced_rows());
     hipStream_t st = (hipStream_t)stream;
-    {
-        const int outW = p->W + 2 * p->pad - p->k + 1;
-        const bool rowStream = p->k == 3 && (p->precision == SG3_CONV_F16X3 || p->precision == SG3_CONV_F16 || p->precision == SG3_CONV_F16X3_F23 ||
-                                             p->precision == SG3_CONV_F16_F23);
-        SG3_REQUIRE(p->outRowStride == 0 || p->outRowStride == outW || (rowStream && p->outRowStride > outW),
-                    "modulated_conv2d: outRowStride must be 0 or outW (a larger pitch is supported by the 3x3 f16x3 / f16 kernels only)");
-    }
-    const bool torgb = p->precision == SG3_CONV_FP32 && p->k == 1 && p->pad == 0 && p->O <= 4 && (size_t)p->I * 4 * sizeof(float) <= 48 * 1024;
-    SG3_REQUIRE(!p->epilogueBias || torgb, "modulated_conv2d: the bias / clamp / scale epilogue exists for the ToRGB kernel only (1x1, O <= 4, fp32 form)");
-    if (p->precision == SG3_CONV_F16X3_F23 || p->precision == SG3_CONV_F16_F23) {
-        SG3_REQUIRE(p->dcoef, "modulated_conv2d: the transform-domain forms need dcoef");
-        SG3_REQUIRE(p->dtype == (p->precision == SG3_CONV_F16X3_F23 ? SG3_F32 : SG3_F16),
-                    "modulated_conv2d: SG3_CONV_F16X3_F23 takes fp32 tensors, SG3_CONV_F16_F23 fp16 tensors");
-        SG3_REQUIRE(f23_supported(p->dtype, p->I, p->O, p->H, p->W, p->k, p->pad, p->outRowStride),
-                    "modulated_conv2d: the transform-domain forms take 3x3 kernels with even W, pad and row pitch (sg3_modconv_f23_supported)");
-        return launch_conv_f23(*p, st);
-    }
-    if (p->precision == SG3_CONV_F16X3 || p->precision == SG3_CONV_F16) {
-        SG3_REQUIRE(p->dcoef, "modulated_conv2d: f16x3 needs dcoef");
-        SG3_REQUIRE(p->k == 3 || p->pad == 0, "modulated_conv2d: f16x3 1x1 kernels take no padding");
-        SG3_REQUIRE(p->k == 3 || ((p->H * p->W) & 1) == 0, "modulated_conv2d: f16x3 1x1 kernels need an even number of pixels (pair loads)");
-        SG3_REQUIRE((int64_t)p->I * p->H * p->W * 4 < (int64_t)1 << 31, "modulated_conv2d: f16x3 needs a sample below 2 GiB (32-bit offsets)");
-        if (p->precision == SG3_CONV_F16) {
-            if (p->k == 1) return p->dtype == SG3_F32 ? dispatch_conv1_f16x3<float, false>(*p, st) : dispatch_conv1_f16x3<_Float16, false>(*p, st);
-            return p->dtype == SG3_F32 ? dispatch_conv_f16x3<float, false>(*p, st) : dispatch_conv_f16x3<_Float16, false>(*p, st);
-        }
-        if (p->k == 1) return p->dtype == SG3_F32 ? dispatch_conv1_f16x3<float, true>(*p, st) : dispatch_conv1_f16x3<_Float16, true>(*p, st);
-        return p->dtype == SG3_F32 ? dispatch_conv_f16x3<float, true>(*p, st) : dispatch_conv_f16x3<_Float16, true>(*p, st);
-    }
-    SG3_REQUIRE(p->precision == SG3_CONV_FP32, "modulated_conv2d: bad precision");
-    if (torgb)
-        return p->dtype == SG3_F32 ? launch_conv_1x1_small<float>(*p, st) : launch_conv_1x1_small<_Float16>(*p, st);
-    if (p->dtype == SG3_F32) return p->k == 3 ? dispatch_conv<float, 3>(*p, st) : dispatch_conv<float, 1>(*p, st);
-    return p->k == 3 ? dispatch_conv<_Float16, 3>(*p, st) : dispatch_conv<_Float16, 1>(*p, st);
+    if (pl.family == SG3_MODCONV_F23) return launch_f23(*p, pl, st);
+    return p->dtype == SG3_F32 ? launch_plan<float>(*p, pl, st) : launch_plan<_Float16>(*p, pl, st);
 }
 
 } // extern "C"

@@ -1,15 +1,40 @@
-// sg3_modconv_f23.h -- interface between sg3_modconv.hip (prep kernels, dispatch) and sg3_modconv_f23.hip (the transform-domain
-// 3x3 kernel, SG3_CONV_F16X3_F23).
+// sg3_modconv_f23.h -- what sg3_modconv.hip (prep kernels, direct kernels, ABI) and sg3_modconv_f23.hip (the transform-domain
+// 3x3 kernel, SG3_CONV_F16X3_F23 / SG3_CONV_F16_F23) share on the host: the launch helpers and the latter's interface.
 #pragma once
 #include "sg3_common.h"
+#include "sg3_modconv_plan.h"
 
 namespace sg3 {
+
+// CUs of the current device, read once per device; 256 without one
+inline int conv_cu_count() {
+    static int cus[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    if (cus[dev] == 0) {
+        int n = 0;
+        cus[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
+    }
+    return cus[dev];
+}
+
+// one planned launch: the dynamic-LDS limit of the instantiation where the plan passes the default 64 KB, then the kernel
+template <typename K, typename... Args>
+static int launch_kernel(K kern, const char* name, const ConvPlan& pl, hipStream_t st, const Args&... args) {
+    if (pl.ldsBytes > 64 * 1024)
+        SG3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, pl.ldsBytes));
+    hipLaunchKernelGGL(kern, dim3(pl.gridX, pl.gridY), dim3(pl.block), pl.ldsBytes, st, args...);
+    SG3_LAUNCH_CHECK(name);
+    return SG3_OK;
+}
 
 int64_t f23_packed_floats(int O, int I, bool split);      // split: hi | lo fragments (SG3_CONV_F16X3_F23); else one fragment per filter row (SG3_CONV_F16_F23)
 // shapes the kernel takes: 3x3, fp32 or fp16 tensors, even W / pad / row pitch (aligned column pairs), 32-bit offsets
 bool f23_supported(int dtype, int I, int O, int H, int W, int k, int pad, int outRowStride);
-int launch_conv_f23(const sg3_modconv_params& q, hipStream_t st);
+int launch_f23(const sg3_modconv_params& q, const ConvPlan& pl, hipStream_t st);      // pl.family == SG3_MODCONV_F23
+int launch_conv_f23(const sg3_modconv_params& q, hipStream_t st);                     // plans, then launches (tools/f23_stamps.hip)
 int f23_force_rows(int rows);          // 4 | 5 | 7, 0 = cost model; returns the previous setting (sg3_modconv_f23_force_rows)
+int f23_forced_rows();                 // the current setting: an input of plan_modconv
 
 // Packing of one output channel's filters (one workgroup per output channel, called from the prep kernels):
 //   [M tile = o / 64][chunk][M block = (o / 32) % 2][xi][ky][hi|lo][lane][8 halfs],  lane = 32 (c / 8) + o % 32,  element = c % 8

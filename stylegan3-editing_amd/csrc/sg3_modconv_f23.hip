@@ -616,80 +616,32 @@ bool f23_supported(int dtype, int I, int O, int H, int W, int k, int pad, int ou
     return true;
 }
 
-template <int TN, typename T>
-static int launch_f23(const sg3_modconv_params& q, hipStream_t st) {
-    constexpr size_t imageBytes = (size_t)2 * (sizeof(T) == 4 ? 16 : 8) * (2 * TN + 2) * 256;
-    constexpr size_t ldsBytes = imageBytes > 65536 ? imageBytes : 65536;       // double-buffered B image, at least the 64 KB exchange area
-    static_assert(ldsBytes <= 160 * 1024, "LDS");
+template <typename T>
+static int launch_f23_rows(const F23Params& p, const ConvPlan& pl, hipStream_t st) {
+    switch (pl.TN) {
+        case 4:  return launch_kernel(modconv_f23_kernel<4, T>, "modconv_f23_kernel", pl, st, p);
+        case 5:  return launch_kernel(modconv_f23_kernel<5, T>, "modconv_f23_kernel", pl, st, p);
+        default: return launch_kernel(modconv_f23_kernel<7, T>, "modconv_f23_kernel", pl, st, p);
+    }
+}
+
+int launch_f23(const sg3_modconv_params& q, const ConvPlan& pl, hipStream_t st) {
+    if (pl.family != SG3_MODCONV_F23) { set_error("modulated_conv2d: grid too large"); return SG3_BAD_ARG; }
     F23Params p;
-    p.x = q.x; p.wp = q.wPacked; p.sIn = q.sIn; p.dcoef = q.dcoef; p.out = q.out;
-    p.N = q.N; p.I = q.I; p.O = q.O; p.H = q.H; p.W = q.W; p.pad = q.pad;
-    p.outH = q.H + 2 * q.pad - 2; p.outW = q.W + 2 * q.pad - 2;
-    p.nch = ceil_div(q.I, 16);
-    p.xTiles = ceil_div(p.outW, 32); p.yTiles = ceil_div(p.outH, 2 * TN); p.mTiles = ceil_div(q.O, 64);
-    const long long total = (long long)p.xTiles * p.yTiles * p.mTiles * q.N;
-    if (total > 0x7fffffffLL) { set_error("modulated_conv2d: grid too large"); return SG3_BAD_ARG; }
-    p.totalBlocks = (int)total;
-    p.outPitch = q.outRowStride > 0 ? q.outRowStride : p.outW;
+    fill_params(p, q, pl);
 #ifdef SG3_F23_STAMPS
     p.stamps = g_f23_stamps;
 #endif
-    auto kern = modconv_f23_kernel<TN, T>;
-    // per device, once: the CU count (grid of persistent workgroups) and this instantiation's dynamic-LDS limit
-    struct DevState { int cus; bool attr; };
-    static DevState devs[64] = {};
-    int dev = 0;
-    SG3_HIP_CHECK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) { set_error("modulated_conv2d: device index %d out of range", dev); return SG3_BAD_ARG; }
-    DevState& ds = devs[dev];
-    if (!ds.attr) {
-        SG3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes));
-        int n = 0;
-        ds.cus = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-        ds.attr = true;
-    }
-    const int cus = ds.cus;
-#ifdef SG3_F23_ONE_TILE
-    const unsigned grid = (unsigned)total;
-#else
-    const unsigned grid = (unsigned)std::min<long long>(total, cus);       // one resident workgroup per CU walks the tiles
-#endif
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), ldsBytes, st, p);
-    SG3_LAUNCH_CHECK("modconv_f23_kernel");
-    return SG3_OK;
+    return q.dtype == SG3_F16 ? launch_f23_rows<_Float16>(p, pl, st) : launch_f23_rows<float>(p, pl, st);
 }
 
 // forced rows per wave: seeded ONCE from the environment (SG3_F23_TN), changed only by an explicit sg3_modconv_f23_force_rows call
-static std::atomic<int> g_f23_rows{[] { const char* fe = getenv("SG3_F23_TN"); const int v = fe ? atoi(fe) : 0; return (v == 4 || v == 5 || v == 7) ? v : 0; }()};
+static std::atomic<int> g_f23_rows{ConvKnobs::env().f23Rows};
 int f23_force_rows(int rows) { return g_f23_rows.exchange((rows == 4 || rows == 5 || rows == 7) ? rows : 0); }
+int f23_forced_rows() { return g_f23_rows.load(std::memory_order_relaxed); }
 
 int launch_conv_f23(const sg3_modconv_params& q, hipStream_t st) {
-    // rows per wave: one workgroup per CU, so the time goes with (rounds of 256 workgroups) x (rows per wave + per-chunk overhead)
-    const int forced = g_f23_rows.load(std::memory_order_relaxed);          // sg3_modconv_f23_force_rows (tests, A/B timing); 0 = cost model
-    const int outH = q.H + 2 * q.pad - 2, outW = q.W + 2 * q.pad - 2;
-    const long long per = (long long)q.N * ceil_div(q.O, 64) * ceil_div(outW, 32);
-    int best = 7; double bestCost = 1e300;
-    const int cands[3] = {7, 5, 4};
-    for (int c = 0; c < 3; c++) {
-        const int tn = cands[c];
-        const long long wgs = per * ceil_div(outH, 2 * tn);
-        const double rounds = wgs <= 1024 ? (double)ceil_div64(wgs, 256) : wgs / 256.0;
-        const double cost = rounds * (tn + 0.6);
-        if (cost < bestCost * 0.999) { bestCost = cost; best = tn; }
-    }
-    if (forced == 4 || forced == 5 || forced == 7) best = forced;
-    if (q.dtype == SG3_F16) {
-        switch (best) {
-            case 4: return launch_f23<4, _Float16>(q, st);
-            case 5: return launch_f23<5, _Float16>(q, st);
-            default: return launch_f23<7, _Float16>(q, st);
-        }
-    }
-    switch (best) {
-        case 4: return launch_f23<4, float>(q, st);
-        case 5: return launch_f23<5, float>(q, st);
-        default: return launch_f23<7, float>(q, st);
-    }
+    return launch_f23(q, plan_modconv(q, conv_cu_count(), ConvKnobs::env(), f23_forced_rows()), st);
 }
 
 } // namespace sg3

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get('SG3_LIB') or os.path.join(_PKG_ROOT, 'lib', 'libsg3hi
 SG3_OK, SG3_NO_KERNEL, SG3_BAD_ARG, SG3_HIP_ERROR = 0, -1, -2, -3
 SG3_F32, SG3_F16, SG3_F64 = 0, 1, 2
 SG3_CONV_FP32, SG3_CONV_F16X3, SG3_CONV_F16, SG3_CONV_F16X3_F23, SG3_CONV_F16_F23 = 0, 1, 2, 3, 4
+SG3_MODCONV_FP32_MFMA, SG3_MODCONV_TORGB, SG3_MODCONV_ROWS, SG3_MODCONV_FLAT, SG3_MODCONV_GEMM1, SG3_MODCONV_F23 = range(6)   # sg3_modconv_dispatch_info.family
 SG3_CONV2D_FORM_F16X3 = 16          # sg3_conv2d_form: first f16x3 form (include/sg3_ops.h)
 _DTYPE = {torch.float32: SG3_F32, torch.float16: SG3_F16, torch.float64: SG3_F64}
 
@@ -57,6 +58,11 @@ class ModconvParams(ctypes.Structure):
                 ('N', c_i32), ('I', c_i32), ('O', c_i32), ('H', c_i32), ('W', c_i32), ('k', c_i32), ('pad', c_i32), ('precision', c_i32),
                 ('epilogueBias', c_vp), ('epilogueClamp', c_f32), ('epilogueScale', c_f32), ('outRowStride', c_i32),
                 ('splitScratch', c_vp), ('splitScratchFloats', c_i64)]
+
+
+class ModconvDispatchInfo(ctypes.Structure):
+    _fields_ = [(n, c_i32) for n in ('family', 'WM', 'WN', 'TM', 'TN', 'SPLIT', 'PACK', 'NBUF', 'M16', 'nch', 'xTiles', 'yTiles', 'mTiles',
+                                     'kSplits', 'totalBlocks', 'gridX', 'gridY', 'block', 'ldsBytes', 'outPitch', 'reduceGrid')]
 
 
 class FourierParams(ctypes.Structure):
@@ -172,6 +178,7 @@ EXPORTS = [
     ('sg3_modconv_packed_floats', ctypes.c_int64, [ctypes.c_int] * 4),
     ('sg3_modulated_conv2d', ctypes.c_int, [ctypes.POINTER(ModconvParams), c_vp]),
     ('sg3_modconv_split_scratch_floats', ctypes.c_int64, [ctypes.POINTER(ModconvParams)]),
+    ('sg3_modconv_dispatch', ctypes.c_int, [ctypes.POINTER(ModconvParams), ctypes.c_int, ctypes.POINTER(ModconvDispatchInfo)]),
     ('sg3_modconv_f23_supported', ctypes.c_int, [ctypes.c_int] * 8),
     ('sg3_modconv_f23_force_rows', ctypes.c_int, [ctypes.c_int]),
     ('sg3_fourier_features', ctypes.c_int, [ctypes.POINTER(FourierParams), c_vp]),

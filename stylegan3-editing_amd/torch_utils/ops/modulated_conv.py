@@ -42,22 +42,7 @@ f23 = {'0': 'off', '1': 'on'}.get(os.environ.get('SG3_CONV_F23', ''), 'auto')
 _F23_FP16_MIN_IO = 4000
 # `align_rows` requests are honoured unless SG3_CONV_DENSE_ROWS=1 (A/B timing of the padded row pitch)
 _ALIGN_ROWS = os.environ.get('SG3_CONV_DENSE_ROWS', '0') != '1'
-
-
-def _composite(x, w, s, demodulate, padding, input_gain):
-    """The reference formulation with plain torch ops (differentiable; also the CPU / impl='ref' path)."""
-    n = int(x.shape[0])
-    o, i, kh, kw = w.shape
-    if demodulate:
-        w = w * w.square().mean([1, 2, 3], keepdim=True).rsqrt()
-        s = s * s.square().mean().rsqrt()
-    w = w.unsqueeze(0) * s.unsqueeze(1).unsqueeze(3).unsqueeze(4)           # [N,O,I,k,k]
-    if demodulate:
-        w = w * (w.square().sum(dim=[2, 3, 4]) + 1e-8).rsqrt().unsqueeze(2).unsqueeze(3).unsqueeze(4)
-    if input_gain is not None:
-        w = w * input_gain.expand(n, i).unsqueeze(1).unsqueeze(3).unsqueeze(4)
-    y = torch.nn.functional.conv2d(x.reshape(1, -1, *x.shape[2:]), w.reshape(-1, i, kh, kw).to(x.dtype), padding=padding, groups=n)
-    return y.reshape(n, -1, *y.shape[2:])
+dispatch_log = None             # set to a list to record the launch plan (sg3_modconv_dispatch: family, tile, grid, K splits) of every call (tests)
 
 
 def _effective_weights(w, s, demodulate, input_gain, n):
@@ -67,12 +52,21 @@ def _effective_weights(w, s, demodulate, input_gain, n):
     if demodulate:
         w = w * w.square().mean([1, 2, 3], keepdim=True).rsqrt()
         s = s * s.square().mean().rsqrt()
-    w = w.unsqueeze(0) * s.unsqueeze(1).unsqueeze(3).unsqueeze(4)
+    w = w.unsqueeze(0) * s.unsqueeze(1).unsqueeze(3).unsqueeze(4)           # [N,O,I,k,k]
     if demodulate:
         w = w * (w.square().sum(dim=[2, 3, 4]) + 1e-8).rsqrt().unsqueeze(2).unsqueeze(3).unsqueeze(4)
     if input_gain is not None:
         w = w * input_gain.expand(n, i).unsqueeze(1).unsqueeze(3).unsqueeze(4)
     return w
+
+
+def _composite(x, w, s, demodulate, padding, input_gain):
+    """The reference formulation with plain torch ops (differentiable; also the CPU / impl='ref' path)."""
+    n = int(x.shape[0])
+    o, i, kh, kw = w.shape
+    w = _effective_weights(w, s, demodulate, input_gain, n)
+    y = torch.nn.functional.conv2d(x.reshape(1, -1, *x.shape[2:]), w.reshape(-1, i, kh, kw).to(x.dtype), padding=padding, groups=n)
+    return y.reshape(n, -1, *y.shape[2:])
 
 
 def _f23_wanted(ci, co, h, wd, padding, fp16=False):
@@ -121,6 +115,34 @@ def _cached_packed_weights(w, key):
     return None
 
 
+def _gain_mode(input_gain, n, ci, dev):
+    """(inputGainMode, float32 device tensor or None) of an input gain [] | [I] | [N,I] (sg3_modconv_prep_params.inputGainMode)."""
+    if input_gain is None:
+        return 0, None
+    g = input_gain.detach().to(device=dev, dtype=torch.float32)
+    if g.numel() == 1:
+        return 1, g.reshape(1)
+    if g.ndim <= 1 or (g.ndim == 2 and g.shape[0] == 1):
+        g = g.reshape(-1).contiguous()
+        assert g.numel() == ci
+        return 2, g
+    return 3, g.expand(n, ci).contiguous()
+
+
+def _choose_form(dtype, k, padding, ci, co, h, wd, bounded):
+    """The arithmetic of a call, as its SG3_CONV_* code (`precision`, `f23` and the shapes each form takes)."""
+    # 1x1: ToRGB (O <= 4) is HBM-bound and has its own kernel; the GEMM kernel loads pixel pairs (even plane size)
+    split = precision == 'f16x3' and (k == 3 or (padding == 0 and co > 4 and (h * wd) % 2 == 0)) and bounded
+    if not split:
+        return abi.SG3_CONV_FP32
+    fp16 = dtype == torch.float16
+    if k == 3 and f23 != 'off' and _f23_wanted(ci, co, h, wd, int(padding), fp16=fp16) \
+            and abi.load().sg3_modconv_f23_supported(abi.dtype_code(dtype), ci, co, h, wd, k, int(padding), 0):
+        # fp16 tensors are the reference's use_fp16 layers: same transform domain, one product per K step
+        return abi.SG3_CONV_F16_F23 if fp16 else abi.SG3_CONV_F16X3_F23
+    return abi.SG3_CONV_F16 if fp16 else abi.SG3_CONV_F16X3
+
+
 def _plan(w, s, demodulate, padding, input_gain, x_bound, x_bound_dev, n, h, wd, dtype, dev, reuse_weights=False):
     """Choose the arithmetic, allocate the prep outputs and fill the prep parameter block (nothing is launched).
     `reuse_weights`: take the packed weights from / leave them in the inference cache above."""
@@ -132,29 +154,12 @@ def _plan(w, s, demodulate, padding, input_gain, x_bound, x_bound_dev, n, h, wd,
     lib = abi.load()
     w32 = w.detach().to(torch.float32).contiguous()
     s32 = s.detach().to(torch.float32).contiguous()
-    gmode, gptr = 0, None
-    if input_gain is not None:
-        g = input_gain.detach().to(device=dev, dtype=torch.float32)
-        if g.numel() == 1:
-            gmode, g = 1, g.reshape(1)
-        elif g.ndim <= 1 or (g.ndim == 2 and g.shape[0] == 1):
-            gmode, g = 2, g.reshape(-1).contiguous()
-            assert g.numel() == ci
-        else:
-            gmode, g = 3, g.expand(n, ci).contiguous()
-        gptr = g
+    gmode, gptr = _gain_mode(input_gain, n, ci, dev)
     if dtype == torch.float16 and x_bound is None and x_bound_dev is None:
         x_bound = 65504.0                                   # the dtype's own range
     bounded = x_bound_dev is not None or (x_bound is not None and x_bound > 0)
-    # 1x1: ToRGB (O <= 4) is HBM-bound and has its own kernel; the GEMM kernel loads pixel pairs (even plane size)
-    split = precision == 'f16x3' and (k == 3 or (padding == 0 and co > 4 and (h * wd) % 2 == 0)) and bounded
-    prec = (abi.SG3_CONV_F16 if dtype == torch.float16 else abi.SG3_CONV_F16X3) if split else abi.SG3_CONV_FP32
-    if prec == abi.SG3_CONV_F16X3 and dtype == torch.float32 and k == 3 and f23 != 'off' and _f23_wanted(ci, co, h, wd, int(padding)) \
-            and lib.sg3_modconv_f23_supported(abi.SG3_F32, ci, co, h, wd, k, int(padding), 0):
-        prec = abi.SG3_CONV_F16X3_F23
-    elif prec == abi.SG3_CONV_F16 and dtype == torch.float16 and k == 3 and f23 != 'off' and _f23_wanted(ci, co, h, wd, int(padding), fp16=True) \
-            and lib.sg3_modconv_f23_supported(abi.SG3_F16, ci, co, h, wd, k, int(padding), 0):
-        prec = abi.SG3_CONV_F16_F23                         # the reference's use_fp16 layers: same transform domain, one product per K step
+    prec = _choose_form(dtype, k, int(padding), ci, co, h, wd, bounded)
+    split = prec != abi.SG3_CONV_FP32
     pr = _Prepared()
     pr.prec = prec
     pr.key = (n, ci, co, k, h, wd, int(padding), dtype)
@@ -245,10 +250,14 @@ def _launch(x, w, s, demodulate, padding, input_gain, x_bound=None, x_bound_dev=
             bias, clamp, scale = epilogue
             bias = bias.detach().to(device=dev, dtype=torch.float32).contiguous()
             cp.epilogueBias, cp.epilogueClamp, cp.epilogueScale = abi.ptr(bias), float(-1.0 if clamp is None else clamp), float(scale)
-        need = int(lib.sg3_modconv_split_scratch_floats(ctypes.byref(cp)))     # > 0: a grid smaller than the chip (batch 1, small maps)
+        need = int(lib.sg3_modconv_split_scratch_floats(ctypes.byref(cp)))     # > 0: the call's plan splits K (a grid smaller than the chip: batch 1, small maps)
         if need > 0:
             scratch = torch.empty([need], dtype=torch.float32, device=dev)
             cp.splitScratch, cp.splitScratchFloats = abi.ptr(scratch), need
+        if dispatch_log is not None:                        # tests: which kernel and tile this call takes (host-only query)
+            info = abi.ModconvDispatchInfo()
+            abi.check(lib.sg3_modconv_dispatch(ctypes.byref(cp), 0, ctypes.byref(info)), 'sg3_modconv_dispatch')
+            dispatch_log.append({name: getattr(info, name) for name, _ in info._fields_})
         abi.check(lib.sg3_modulated_conv2d(ctypes.byref(cp), stream), 'sg3_modulated_conv2d')
     return out, pr.s_in, pr.dcoef
 
@@ -346,15 +355,7 @@ def _modulation_grads(dw_eff, w, s, input_gain, demodulate):
     g_eff = dw_eff.to(torch.float32).contiguous()
     w32 = w.detach().to(torch.float32).contiguous()
     s32 = s.detach().to(torch.float32).contiguous()
-    gmode, gptr = 0, None
-    if input_gain is not None:
-        g = input_gain.detach().to(device=dev, dtype=torch.float32)
-        if g.numel() == 1:
-            gmode, gptr = 1, g.reshape(1)
-        elif g.ndim <= 1 or (g.ndim == 2 and g.shape[0] == 1):
-            gmode, gptr = 2, g.reshape(-1).contiguous()
-        else:
-            gmode, gptr = 3, g.expand(n, ci).contiguous()
+    gmode, gptr = _gain_mode(input_gain, n, ci, dev)
     dw = torch.empty([co, ci, k, k], dtype=torch.float32, device=dev)
     ds = torch.empty([n, ci], dtype=torch.float32, device=dev)
     scratch = torch.empty([co + n * ci], dtype=torch.float32, device=dev)
@@ -405,28 +406,29 @@ class _ModulatedConv2dHip(torch.autograd.Function):
         co, ci, k, _ = (int(v) for v in w.shape)
         if need[0]:
             out[0] = _data_gradient(dy, w, s_in, dcoef if dcoef.numel() else None, demodulate, padding, dy_amax=dy_amax)
-        if (need[1] or need[2]) and not (has_gain and need[3]) and _MODGRAD_KERNELS:
-            # gradient of the per-sample effective weights (weight-gradient kernel), then the chain rule to w and s in closed form
-            x_amax = None
-            if ctx.x_bound is not None and ctx.x_bound > 0:
-                x_amax = _bound_scalar(ctx.x_bound, x.device)            # the layer's own bound: no pass over x
-            dw_eff = _weight_gradient(x, dy, k, padding, x_amax=x_amax, dy_amax=dy_amax)
+        if not (need[1] or need[2] or (has_gain and need[3])):
+            return tuple(out)
+        kernels = not (has_gain and need[3]) and _MODGRAD_KERNELS
+        if not kernels:
+            # input_gain needs a gradient too, or the kernels are switched off: the chain rule through the small [N,O,I,k,k]
+            # tensor for w, s and input_gain goes through autograd
+            with torch.enable_grad():
+                wd = w.detach().requires_grad_(need[1]); sd = s.detach().requires_grad_(need[2])
+                gd = g.detach().requires_grad_(need[3]) if has_gain else None
+                w_eff = _effective_weights(wd.float(), sd.float(), demodulate, gd, n)
+        # gradient of the per-sample effective weights (weight-gradient kernel)
+        x_amax = None
+        if ctx.x_bound is not None and ctx.x_bound > 0:
+            x_amax = _bound_scalar(ctx.x_bound, x.device)            # the layer's own bound: no pass over x
+        dw_eff = _weight_gradient(x, dy, k, padding, x_amax=x_amax, dy_amax=dy_amax)
+        if kernels:
+            # the chain rule to w and s in closed form
             dw, ds = _modulation_grads(dw_eff, w, s, g if has_gain else None, demodulate)
             if need[1]:
                 out[1] = dw.to(w.dtype)
             if need[2]:
                 out[2] = ds.to(s.dtype)
-        elif need[1] or need[2] or (has_gain and need[3]):
-            # the same through autograd (input_gain needs a gradient too, or the kernels are switched off): the chain rule
-            # through the small [N,O,I,k,k] tensor for w, s and input_gain
-            with torch.enable_grad():
-                wd = w.detach().requires_grad_(need[1]); sd = s.detach().requires_grad_(need[2])
-                gd = g.detach().requires_grad_(need[3]) if has_gain else None
-                w_eff = _effective_weights(wd.float(), sd.float(), demodulate, gd, n)
-            x_amax = None
-            if ctx.x_bound is not None and ctx.x_bound > 0:
-                x_amax = _bound_scalar(ctx.x_bound, x.device)            # the layer's own bound: no pass over x
-            dw_eff = _weight_gradient(x, dy, k, padding, x_amax=x_amax, dy_amax=dy_amax)
+        else:
             ins, idx = [], []
             for j, t in ((1, wd), (2, sd), (3, gd)):
                 if t is not None and need[j]:

@@ -1,0 +1,60 @@
+// modconv_dispatch_recorder.h -- force-included (-include) in front of csrc/sg3_modconv.hip and csrc/sg3_modconv_f23.hip to
+// record what their host side WOULD launch, without a GPU: the launch macro, the dynamic-LDS attribute call and the device
+// queries are replaced after <hip/hip_runtime.h> has declared the real ones.  Used once per change of the dispatch to regenerate
+// tests/golden/modconv_dispatch.json (see make_modconv_dispatch.py); never part of the product library.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cxxabi.h>
+#include <dlfcn.h>
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+
+namespace rec {
+
+inline std::string& log() { static std::string s; return s; }
+inline int& pending_attr() { static int v = 0; return v; }
+
+// demangled name of a kernel's host stub, template arguments included (link with -rdynamic, default visibility)
+inline std::string kernel_name(const void* f) {
+    Dl_info info;
+    if (!dladdr(f, &info) || !info.dli_sname) return "?";
+    std::string m = info.dli_sname;
+    for (size_t i; (i = m.find("DF16_")) != std::string::npos;) m.replace(i, 5, "Dh");      // _Float16 as `half`: older demanglers stop at DF16_
+    int st = 0;
+    char* d = abi::__cxa_demangle(m.c_str(), nullptr, nullptr, &st);
+    std::string s = d ? d : m;
+    free(d);
+    return s;
+}
+
+// tile geometry of the parameter block a convolution kernel takes (ConvParams / F23Params); other first arguments have none
+template <class P> auto geometry(const P& p, int) -> decltype((void)p.xTiles, std::string()) {
+    char b[160];
+    snprintf(b, sizeof b, ",\"nch\":%d,\"xTiles\":%d,\"yTiles\":%d,\"mTiles\":%d,\"outPitch\":%d", p.nch, p.xTiles, p.yTiles, p.mTiles, p.outPitch);
+    return b;
+}
+template <class P> std::string geometry(const P&, long) { return ""; }
+
+template <class K, class A0, class... R>
+inline void launch(K kern, dim3 g, dim3 b, size_t lds, const A0& a0, const R&...) {
+    char buf[256];
+    snprintf(buf, sizeof buf, "\",\"grid\":[%u,%u,%u],\"block\":%u,\"lds\":%zu,\"attr\":%d", g.x, g.y, g.z, b.x, lds, pending_attr());
+    pending_attr() = 0;
+    std::string& s = log();
+    if (!s.empty()) s += ",";
+    s += "{\"kernel\":\"" + kernel_name(reinterpret_cast<const void*>(kern)) + buf + geometry(a0, 0) + "}";
+}
+
+inline hipError_t func_attr(const void*, hipFuncAttribute, int v) { pending_attr() = v; return hipSuccess; }
+inline hipError_t no_device(int* dev) { *dev = 0; return hipSuccess; }
+inline hipError_t cu_count(int* n) { const char* e = getenv("REC_CUS"); *n = e ? atoi(e) : 256; return hipSuccess; }
+
+} // namespace rec
+
+#undef hipLaunchKernelGGL
+#define hipLaunchKernelGGL(kern, grid, block, lds, st, ...) rec::launch(kern, grid, block, (size_t)(lds), __VA_ARGS__)
+#define hipFuncSetAttribute(f, a, v) rec::func_attr(f, a, v)
+#define hipGetLastError() hipSuccess
+#define hipGetDevice(p) rec::no_device(p)
+#define hipDeviceGetAttribute(p, a, d) rec::cu_count(p)

@@ -9,6 +9,7 @@ import torch
 
 from golden_cases import BIAS_ACT_CASES, FLRELU_CASES, FLRELU_GRAD_CASES, MODCONV_CASES, UPFIRDN_CASES, make_filter, rand
 from helpers import golden, maxabs, oracle_design, product_design
+from torch_utils import _sg3abi as A
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -340,6 +341,24 @@ def test_bias_act_gradients(act):
         assert maxabs(a, r) <= 1e-7 * max(1.0, float(np.abs(r).max()))   # gain (sqrt 2) crosses the ABI as fp32, as in the reference
 
 
+class _modconv_plans:
+    """Records, for every modulated convolution launched inside the block, the plan the library made for it (sg3_modconv_dispatch)."""
+
+    def __enter__(self):
+        from torch_utils.ops import modulated_conv as mc
+        mc.dispatch_log = self.log = []
+        return self.log
+
+    def __exit__(self, *exc):
+        from torch_utils.ops import modulated_conv as mc
+        mc.dispatch_log = None
+
+
+def _tile(plan):
+    """(family, WM, WN, TN, PACK) of a recorded plan"""
+    return tuple(plan[n] for n in ('family', 'WM', 'WN', 'TN', 'PACK'))
+
+
 @pytest.mark.parametrize('name', sorted(MODCONV_CASES))
 def test_modulated_conv2d(name):
     from models.stylegan3.networks_stylegan3 import modulated_conv2d
@@ -394,7 +413,8 @@ def test_modulated_conv2d_plane_beyond_descriptor_offsets(k):
 
 
 @pytest.mark.parametrize('n,ci,co,h', [(2, 323, 203, 22), (1, 128, 81, 40), (2, 51, 32, 70), (2, 512, 512, 12), (1, 203, 128, 37), (3, 81, 51, 50),
-                                      (4, 16, 832, 36),         # 520 eight-row tiles -> the ten-row tile (one round of 416)
+                                      (4, 16, 832, 36),         # 520 eight-row tiles: one round of 468 flat runs instead (the ten-row tile's shape before the flat kernel)
+                                      (1, 16, 640, 96),         # 520 eight-row tiles -> the ten-row tile (one round of 400); 101 columns are too wide for flat runs
                                       (8, 96, 100, 36), (2, 70, 512, 52), (1, 64, 64, 35), (8, 512, 512, 36)])   # narrow planes: flat pixel runs (2 - 4 per wave)
 def test_modulated_conv2d_split_precision(n, ci, co, h):
     """fp16 hi/lo split on the fp16 matrix cores (x_bound given) is fp32-equivalent: compared with the fp64 result of
@@ -409,10 +429,18 @@ def test_modulated_conv2d_split_precision(n, ci, co, h):
     for prec in ('f16x3', 'fp32'):
         mc.precision = prec
         try:
-            y = mc.modulated_conv2d(T(x), T(w), T(s), demodulate=True, padding=2, input_gain=torch.tensor(0.8, device=DEV), x_bound=256.0)
+            with _modconv_plans() as plans:
+                y = mc.modulated_conv2d(T(x), T(w), T(s), demodulate=True, padding=2, input_gain=torch.tensor(0.8, device=DEV), x_bound=256.0)
         finally:
             mc.precision = 'f16x3'
         errs[prec] = maxabs(y.cpu().numpy(), ref) / scale
+        assert len(plans) == 1
+        if prec == 'fp32':
+            assert plans[0]['family'] == A.SG3_MODCONV_FP32_MFMA
+        elif (n, ci, co, h) == (1, 16, 640, 96):
+            assert _tile(plans[0]) == (A.SG3_MODCONV_ROWS, 2, 2, 5, 0), plans[0]                 # 64 channels x (2 x 5 rows x 32 columns)
+        elif (n, ci, co, h) in ((4, 16, 832, 36), (8, 96, 100, 36), (2, 70, 512, 52), (1, 64, 64, 35), (8, 512, 512, 36)):
+            assert plans[0]['family'] == A.SG3_MODCONV_FLAT and 2 <= plans[0]['TN'] <= 4, plans[0]
     print('relative max errors vs fp64:', errs)
     assert errs['fp32'] <= 5e-6 and errs['f16x3'] <= 5e-6, errs     # K up to 4608 fp32 accumulation
     # styles of magnitude 1e3: |x * s| would overflow fp16 without the per-sample power-of-two rescale
@@ -453,7 +481,7 @@ def test_modulated_conv2d_split_precision_1x1(n, ci, co, h):
 
 
 @pytest.mark.parametrize('n,ci,co,h,k', [(2, 203, 128, 37, 3), (1, 81, 51, 50, 3), (2, 645, 406, 20, 1), (1, 64, 64, 33, 1),
-                                         (1, 64, 128, 131, 3), (1, 51, 32, 140, 3), (1, 81, 51, 127, 3), (1, 33, 70, 150, 3)])
+                                         (1, 64, 128, 131, 3), (1, 51, 32, 140, 3), (1, 81, 51, 127, 3), (1, 33, 70, 150, 3), (1, 32, 32, 126, 3)])
 def test_modulated_conv2d_fp16_form(n, ci, co, h, k):
     """fp16 tensors take the single-MFMA fp16 form (SG3_CONV_F16): equal to the fp64 result for operands rounded to
     fp16 up to fp16 rounding of (x * s), of the weights and of the output.  Outputs of 128 rows or more take the taller row
@@ -462,11 +490,30 @@ def test_modulated_conv2d_fp16_form(n, ci, co, h, k):
     from torch_utils.ops import modulated_conv as mc
     x = np.clip(rand(91, n, ci, h, h + 3) * 20, -256, 256).astype(np.float16); w = rand(92, co, ci, k, k); s = rand(93, n, ci) + 1
     ref = O.modulated_conv2d(x.astype(np.float64), w.astype(np.float64), s.astype(np.float64), True, k - 1, 0.8)
-    y = mc.modulated_conv2d(T(x), T(w), T(s), demodulate=True, padding=k - 1, input_gain=torch.tensor(0.8, device=DEV))
-    assert y.dtype == torch.float16 and tuple(y.shape) == ref.shape
-    err = np.abs(y.float().cpu().numpy() - ref)
     scale = float(np.abs(ref).max())
-    assert err.max() <= 4e-3 * scale and err.mean() <= 4e-4 * scale
+
+    def check():
+        with _modconv_plans() as plans:
+            y = mc.modulated_conv2d(T(x), T(w), T(s), demodulate=True, padding=k - 1, input_gain=torch.tensor(0.8, device=DEV))
+        assert y.dtype == torch.float16 and tuple(y.shape) == ref.shape
+        err = np.abs(y.float().cpu().numpy() - ref)
+        assert err.max() <= 4e-3 * scale and err.mean() <= 4e-4 * scale
+        assert len(plans) == 1 and plans[0]['SPLIT'] == 0
+        return plans[0]
+
+    plan = check()
+    tall = {(1, 64, 128, 131): (2, 2, 6, 0), (1, 81, 51, 127): (2, 2, 6, 1), (1, 51, 32, 140): (1, 4, 5, 1), (1, 33, 70, 150): (1, 4, 5, 1),
+            (1, 32, 32, 126): (1, 4, 5, 0)}.get((n, ci, co, h))
+    if tall is not None:                                    # (WM, WN, rows per wave, packed K tail) of the taller stacks
+        if plan['family'] == A.SG3_MODCONV_F23:
+            # even widths with 48 channels or more go to the fp16 transform-domain form by default (test_gpu_f23.py) since it
+            # exists: the direct kernel's six-row stack is run as well, and held to the same bounds
+            saved, mc.f23 = mc.f23, 'off'
+            try:
+                plan = check()
+            finally:
+                mc.f23 = saved
+        assert _tile(plan) == (A.SG3_MODCONV_ROWS,) + tall, plan
     mc.precision = 'fp32'
     try:
         y32 = mc.modulated_conv2d(T(x), T(w), T(s), demodulate=True, padding=k - 1, input_gain=torch.tensor(0.8, device=DEV))
@@ -915,7 +962,8 @@ def test_modulated_conv2d_k_split_on_small_grids_matches_the_unsplit_kernel(n, c
             return getattr(lib, name)
 
     with torch.no_grad():
-        split = mc.modulated_conv2d(x=x, w=w, s=s, padding=k - 1, demodulate=True, x_bound=float(x.abs().max()) * 1.01)
+        with _modconv_plans() as plans:
+            split = mc.modulated_conv2d(x=x, w=w, s=s, padding=k - 1, demodulate=True, x_bound=float(x.abs().max()) * 1.01)
         saved = _sg3abi._lib
         _sg3abi._lib = _NoScratch()
         try:
@@ -926,5 +974,8 @@ def test_modulated_conv2d_k_split_on_small_grids_matches_the_unsplit_kernel(n, c
     scale = float(ref.abs().max())
     assert float((split.double() - ref).abs().max()) <= 2e-6 * scale and float((plain.double() - ref).abs().max()) <= 3e-6 * scale
     assert float((split - plain).abs().max()) <= 4e-6 * scale          # two fp32 summation orders over K = 9 I
+    assert len(plans) == 1 and plans[0]['kSplits'] >= 1
     if (n, ci, co, h) in ((1, 512, 512, 36), (1, 1024, 1024, 36)):      # L0 - L2 of a batch-1 PTI step (T: flat kernel, 96 tiles; R: 1x1 GEMM, 24 tiles): four splits
+        assert plans[0]['kSplits'] == 4 and plans[0]['family'] == (A.SG3_MODCONV_FLAT if k == 3 else A.SG3_MODCONV_GEMM1), plans[0]
+        assert plans[0]['reduceGrid'] > 0 and plans[0]['gridX'] == 4 * (96 if k == 3 else 24)
         assert not torch.equal(split, plain)                            # the split path did run
