@@ -819,6 +819,107 @@ SG3_API int sg3_clip_gemm(const sg3_clip_gemm_params* p, void* stream);
 SG3_API int sg3_clip_attention(const sg3_clip_attention_params* p, void* stream);
 SG3_API int sg3_clip_embed(const sg3_clip_embed_params* p, void* stream);
 
+/* ----------------------------------------------------------------------
+ * Backward of the CLIP image tower with respect to its input (weights frozen: there is no weight gradient).  One launch per call, no atomics, fixed summation order: a row's result depends on that row's inputs only.
+ *
+ * sg3_clip_gemm_grad: the GEMM of sg3_clip_gemm (same kernel, same sizes and alignment rules, same accumulation order) with the
+ *   epilogues of the recording forward and of the data-gradient pass; dX = dY . W is this kernel on a float16 [in][out] copy of
+ *   the matrix.  epilogue is SG3_CLIP_EPI_F32, SG3_CLIP_EPI_F16 (as sg3_clip_gemm), or:
+ *     SG3_CLIP_EPI_RESIDUAL            out float32 [M][N] = aux[m][n] + acc + bias: the residual is read from aux (float32 [M][N],
+ *                                      required), so the stream before the block stays as the backward needs it
+ *     SG3_CLIP_EPI_QUICKGELU_SAVE_F16  as SG3_CLIP_EPI_QUICKGELU_F16, and aux float16 [M][N] = v (the pre-activation)
+ *     SG3_CLIP_EPI_DQUICKGELU_F16      out float16 [M][N] = v * QuickGELU'(u), u = aux[m][n] (float16, read),
+ *                                      QuickGELU'(u) = s (1 + 1.702 u (1 - s)), s = sigmoid(1.702 u), in float32
+ *     SG3_CLIP_EPI_PATCH_ADJOINT       the adjoint of SG3_CLIP_EPI_PATCH with respect to the image: a is the token gradient
+ *                                      [B][g*g + 1][K] (row m of the product is token 1 + m % g^2 of sample m / g^2), w is
+ *                                      conv1.weight transposed, float16 [N = 3*P*P][K]; out float32 [B][3][R][R], element
+ *                                      (b, c, py*P + ky, px*P + kx) = v * (scale ? scale[b] : 1) with n = (c*P + ky)*P + kx.
+ *                                      Patches do not overlap: every pixel of the g*P x g*P area is written once, no other is.
+ *   aF32 != 0: a is float32 [M][K] (16-byte aligned) and rounded to float16 as it is loaded; allowed for SG3_CLIP_EPI_F16,
+ *   SG3_CLIP_EPI_DQUICKGELU_F16 and SG3_CLIP_EPI_PATCH_ADJOINT (the float32 gradient stream is the operand).
+ *
+ * sg3_clip_layernorm_bwd: for y = LayerNorm(x) * gamma + beta and dy [rows][D] (row r at dy + r * dyRowStride),
+ *   dx = rstd (g - mean(g) - xhat mean(g xhat)), g = gamma dy, with the statistics of x taken as the forward takes them (relative to
+ *   the row's first element).  Row r of x at x + r * xRowStride, of dx at dx + r * dxRowStride.  accumulate != 0: dx += result
+ *   (the float32 gradient stream), else dx = result; dx == dy is allowed (every element is read and written by one lane).
+ *
+ * sg3_clip_attention_bwd: qkv float16 [B][L][3*D] as saved by the forward, dout float16 [B][L][D]; dqkv float16 [B][L][3*D].
+ *   The probabilities are recomputed per (sample, head) in LDS; scores, softmax and its backward
+ *   dS = P (dP - sum_j P dP) are float32.  L <= 128, head dimension 64.  causal != 0 is refused with SG3_BAD_ARG.
+ *
+ * sg3_clip_grad_scale: per row b of g float32 [B][E]: scale[b] = 2^(4 - e) with max|g[b]| = m 2^e, 0.5 <= m < 1 (1 for a zero or
+ *   non-finite row), so that max|g[b]| scale[b] is in [8, 16); out16 float16 [B][E] = g scale[b]; inv[b] = 1 / scale[b] (exact).
+ *   The gradients of a float16 backward are below float16's normal range at their natural size; the power of two is carried
+ *   through the (linear) backward and divided out at the image.  Taken on the device: no host synchronisation.
+ * ---------------------------------------------------------------------- */
+#define SG3_CLIP_EPI_QUICKGELU_SAVE_F16 5
+#define SG3_CLIP_EPI_DQUICKGELU_F16     6
+#define SG3_CLIP_EPI_PATCH_ADJOINT      7
+
+typedef struct sg3_clip_gemm_grad_params {
+    const void*    a;              /* float16 [M][K], or float32 when aF32; SG3_CLIP_EPI_PATCH_ADJOINT: [B][g*g + 1][K] */
+    const void*    w;              /* float16 [N][K] */
+    const float*   bias;           /* [N] or NULL */
+    void*          out;
+    void*          aux;            /* see the epilogues; NULL for the others */
+    const float*   scale;          /* SG3_CLIP_EPI_PATCH_ADJOINT: [B] or NULL */
+    int32_t        M, K, N;
+    int32_t        epilogue;
+    int32_t        P, R;           /* SG3_CLIP_EPI_PATCH_ADJOINT: patch size, image resolution */
+    int32_t        aF32;
+} sg3_clip_gemm_grad_params;
+
+typedef struct sg3_clip_layernorm_bwd_params {
+    const float*   dy;
+    const float*   x;
+    const float*   gamma;          /* [D] */
+    float*         dx;
+    int64_t        dyRowStride, xRowStride, dxRowStride;
+    int32_t        rows, D;
+    int32_t        accumulate;
+    float          eps;
+} sg3_clip_layernorm_bwd_params;
+
+typedef struct sg3_clip_attention_bwd_params {
+    const void*    qkv;            /* float16 [B][L][3*64*heads] */
+    const void*    dout;           /* float16 [B][L][64*heads] */
+    void*          dqkv;           /* float16 [B][L][3*64*heads] */
+    int32_t        B, L, heads;
+    int32_t        causal;
+} sg3_clip_attention_bwd_params;
+
+typedef struct sg3_clip_grad_scale_params {
+    const float*   g;              /* [B][E] */
+    void*          out16;          /* float16 [B][E] */
+    float*         inv;            /* [B] */
+    int32_t        B, E;
+} sg3_clip_grad_scale_params;
+
+SG3_API int sg3_clip_gemm_grad(const sg3_clip_gemm_grad_params* p, void* stream);
+SG3_API int sg3_clip_layernorm_bwd(const sg3_clip_layernorm_bwd_params* p, void* stream);
+SG3_API int sg3_clip_attention_bwd(const sg3_clip_attention_bwd_params* p, void* stream);
+SG3_API int sg3_clip_grad_scale(const sg3_clip_grad_scale_params* p, void* stream);
+
+/* ----------------------------------------------------------------------
+ * Image preparation of the CLIP loss (reference criteria/clip_loss.py: AvgPool2d(k)(Upsample(scale_factor=up)(x)), nearest):
+ *     y[oy][ox] = (1 / k^2) sum_{u in [oy k, oy k + k)} sum_{v in [ox k, ox k + k)} x[u / up][v / up],   oh = (up H) / k, ow = (up W) / k
+ * as one launch with no intermediate: per axis the window covers at most ceil(k / up) + 1 source pixels, each with an integer
+ * count of upsampled pixels inside the window.  adjoint != 0 runs the transpose in gather form: x is then the OUTPUT [B][C][H][W]
+ * (the gradient of the source) and y the INPUT [B][C][oh][ow]; every source pixel sums the windows that overlap it (no atomics).
+ * float32, strides in elements (n, c, y, x), any layout; the written tensor must not overlap the read one.
+ * ---------------------------------------------------------------------- */
+typedef struct sg3_clip_resample_params {
+    float*         x;              /* [B][C][H][W]: read (forward) or written (adjoint) */
+    int64_t        xStride[4];
+    float*         y;              /* [B][C][oh][ow]: written (forward) or read (adjoint) */
+    int64_t        yStride[4];
+    int32_t        B, C, H, W, oh, ow;
+    int32_t        up, k;
+    int32_t        adjoint;
+} sg3_clip_resample_params;
+
+SG3_API int sg3_clip_resample(const sg3_clip_resample_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

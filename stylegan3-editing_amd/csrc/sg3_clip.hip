@@ -16,6 +16,11 @@
 //
 // The patch-embedding form gathers A from the fp32 NCHW image: the convolution's stride equals its kernel, so row m is patch
 // (sample, py, px) and k = (c * P + ky) * P + kx; 8 consecutive k are 8 consecutive pixels of one image row (P % 8 == 0).
+//
+// sg3_clip_gemm_grad is a second entry point of the same kernel for the recording forward and the backward of the image tower
+// (the rest of that backward is sg3_clip_grad.hip): dX = dY . W on [in][out] copies of the matrices, with the epilogues
+// residual-from-aux, QuickGELU + saved pre-activation, x QuickGELU'(u), and the patch-embedding adjoint, and with a float32 A
+// operand (the gradient stream) rounded to float16 as it is loaded.
 #include "sg3_common.h"
 
 namespace sg3 {
@@ -73,25 +78,47 @@ static constexpr int SEGS = TK / 8;                      // 16-byte segments per
 static constexpr int LOADS = TM * SEGS / 256;            // segments per thread, per operand and stage
 static_assert(TK % 32 == 0 && LOADS >= 1, "stage depth");
 
-template <int EPI>
-__device__ __forceinline__ uint4 load_a(const sg3_clip_gemm_params& p, int m, int k) {
-    uint4 r = make_uint4(0, 0, 0, 0);
-    if (m >= p.M || k >= p.K) return r;
-    if (EPI != SG3_CLIP_EPI_PATCH) return *(const uint4*)((const _Float16*)p.a + (int64_t)m * p.K + k);
-    const int g = p.R / p.P, gg = g * g, PP = p.P * p.P;
-    const int b = m / gg, pi = m - b * gg, py = pi / g, px = pi - py * g;
-    const int c = k / PP, rem = k - c * PP, ky = rem / p.P, kx = rem - ky * p.P;
-    const float* src = (const float*)p.a + (((int64_t)b * 3 + c) * p.R + (py * p.P + ky)) * p.R + (px * p.P + kx);
+// the kernel's arguments: what sg3_clip_gemm_params and sg3_clip_gemm_grad_params hold between them (the epilogue is a template argument)
+struct gemm_args {
+    const void* a; const void* w; const float* bias; void* out; const float* pos; const float* cls; void* aux; const float* scale;
+    int32_t M, K, N, P, R;
+};
+
+__device__ __forceinline__ uint4 halfs_of(const float* src) {
     const float4 lo = *(const float4*)src, hi = *(const float4*)(src + 4);
     half8 h = {(_Float16)lo.x, (_Float16)lo.y, (_Float16)lo.z, (_Float16)lo.w, (_Float16)hi.x, (_Float16)hi.y, (_Float16)hi.z, (_Float16)hi.w};
     return *(uint4*)&h;
 }
 
-__device__ __forceinline__ float quick_gelu(float v) { return v / (1.0f + __expf(-1.702f * v)); }
+// A32: a is float32 and rounded to float16 here (the gradient stream as an operand).  The patch adjoint reads token 1 + patch of
+// each sample: row m of the product is row (m / g^2) (g^2 + 1) + 1 + m % g^2 of a.
+template <int EPI, bool A32>
+__device__ __forceinline__ uint4 load_a(const gemm_args& p, int m, int k) {
+    uint4 r = make_uint4(0, 0, 0, 0);
+    if (m >= p.M || k >= p.K) return r;
+    if (EPI != SG3_CLIP_EPI_PATCH) {
+        int64_t row = m;
+        if (EPI == SG3_CLIP_EPI_PATCH_ADJOINT) { const int g = p.R / p.P, gg = g * g; row = (int64_t)(m / gg) * (gg + 1) + 1 + m % gg; }
+        if (A32) return halfs_of((const float*)p.a + row * p.K + k);
+        return *(const uint4*)((const _Float16*)p.a + row * p.K + k);
+    }
+    const int g = p.R / p.P, gg = g * g, PP = p.P * p.P;
+    const int b = m / gg, pi = m - b * gg, py = pi / g, px = pi - py * g;
+    const int c = k / PP, rem = k - c * PP, ky = rem / p.P, kx = rem - ky * p.P;
+    const float* src = (const float*)p.a + (((int64_t)b * 3 + c) * p.R + (py * p.P + ky)) * p.R + (px * p.P + kx);
+    return halfs_of(src);
+}
 
-template <int EPI>
+__device__ __forceinline__ float quick_gelu(float v) { return v / (1.0f + __expf(-1.702f * v)); }
+// d/du [u sigmoid(1.702 u)] = s (1 + 1.702 u (1 - s)); expf, not __expf: the derivative multiplies every gradient of the MLP branch
+__device__ __forceinline__ float quick_gelu_grad(float u) {
+    const float s = 1.0f / (1.0f + expf(-1.702f * u));
+    return s * (1.0f + 1.702f * u * (1.0f - s));
+}
+
+template <int EPI, bool A32>
 __global__ void __launch_bounds__(256)
-clip_gemm_kernel(sg3_clip_gemm_params p) {
+clip_gemm_kernel(gemm_args p) {
     __shared__ __attribute__((aligned(16))) _Float16 sA[2][TM * PITCH];
     __shared__ __attribute__((aligned(16))) _Float16 sW[2][TN * PITCH];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -112,7 +139,7 @@ clip_gemm_kernel(sg3_clip_gemm_params p) {
 #pragma unroll
         for (int s = 0; s < LOADS; s++) {
             const int e = tid + 256 * s, row = e / SEGS, k = k0 + (e % SEGS) * 8;
-            ra[s] = load_a<EPI>(p, m0 + row, k);
+            ra[s] = load_a<EPI, A32>(p, m0 + row, k);
             rw[s] = k < p.K ? *(const uint4*)((const _Float16*)p.w + (int64_t)(n0 + row) * p.K + k) : make_uint4(0, 0, 0, 0);
         }
     };
@@ -148,7 +175,7 @@ clip_gemm_kernel(sg3_clip_gemm_params p) {
         __syncthreads();
     }
 
-    const int g = EPI == SG3_CLIP_EPI_PATCH ? p.R / p.P : 1, gg = g * g;
+    const int g = (EPI == SG3_CLIP_EPI_PATCH || EPI == SG3_CLIP_EPI_PATCH_ADJOINT) ? p.R / p.P : 1, gg = g * g;
 #pragma unroll
     for (int i = 0; i < 2; i++)
 #pragma unroll
@@ -164,8 +191,17 @@ clip_gemm_kernel(sg3_clip_gemm_params p) {
                 if (EPI == SG3_CLIP_EPI_F32) ((float*)p.out)[o] = v;
                 else if (EPI == SG3_CLIP_EPI_F16) ((_Float16*)p.out)[o] = (_Float16)v;
                 else if (EPI == SG3_CLIP_EPI_QUICKGELU_F16) ((_Float16*)p.out)[o] = (_Float16)quick_gelu(v);
-                else if (EPI == SG3_CLIP_EPI_RESIDUAL) ((float*)p.out)[o] += v;
-                else {
+                else if (EPI == SG3_CLIP_EPI_RESIDUAL) ((float*)p.out)[o] = (p.aux ? (const float*)p.aux : (const float*)p.out)[o] + v;
+                else if (EPI == SG3_CLIP_EPI_QUICKGELU_SAVE_F16) {
+                    ((_Float16*)p.aux)[o] = (_Float16)v;
+                    ((_Float16*)p.out)[o] = (_Float16)quick_gelu(v);
+                } else if (EPI == SG3_CLIP_EPI_DQUICKGELU_F16) ((_Float16*)p.out)[o] = (_Float16)(v * quick_gelu_grad((float)((const _Float16*)p.aux)[o]));
+                else if (EPI == SG3_CLIP_EPI_PATCH_ADJOINT) {
+                    const int PP = p.P * p.P;
+                    const int b = m / gg, pi = m - b * gg, py = pi / g, px = pi - py * g;
+                    const int c = n / PP, rem = n - c * PP, ky = rem / p.P, kx = rem - ky * p.P;
+                    ((float*)p.out)[(((int64_t)b * 3 + c) * p.R + (py * p.P + ky)) * p.R + (px * p.P + kx)] = p.scale ? v * p.scale[b] : v;
+                } else {
                     const int b = m / gg, pi = m - b * gg;
                     float* tok = (float*)p.out + ((int64_t)b * (gg + 1)) * p.N + n;
                     tok[(int64_t)(1 + pi) * p.N] = v + p.pos[(int64_t)(1 + pi) * p.N + n];
@@ -251,9 +287,9 @@ clip_embed_kernel(sg3_clip_embed_params p) {
 
 static inline bool aligned16(const void* q) { return ((uintptr_t)q & 15) == 0; }
 
-template <int EPI>
-static int launch_gemm(const sg3_clip_gemm_params* p, hipStream_t s) {
-    hipLaunchKernelGGL(clip_gemm_kernel<EPI>, dim3(p->N / TN, ceil_div(p->M, TM)), dim3(256), 0, s, *p);
+template <int EPI, bool A32 = false>
+static int launch_gemm(const gemm_args& p, hipStream_t s) {
+    hipLaunchKernelGGL((clip_gemm_kernel<EPI, A32>), dim3(p.N / TN, ceil_div(p.M, TM)), dim3(256), 0, s, p);
     SG3_LAUNCH_CHECK("clip_gemm_kernel");
     return SG3_OK;
 }
@@ -279,12 +315,16 @@ int sg3_clip_layernorm(const sg3_clip_layernorm_params* p, void* stream) {
     return SG3_OK;
 }
 
+// what both GEMM entry points check: sizes, alignment, grid
+#define SG3_CLIP_GEMM_COMMON(name)                                                                                                      \
+    SG3_REQUIRE(p && p->a && p->w && p->out, name ": null tensor");                                                                     \
+    SG3_REQUIRE(p->M > 0 && p->N > 0 && p->K > 0, name ": sizes must be positive (M %d, N %d, K %d)", p->M, p->N, p->K);                \
+    SG3_REQUIRE(p->N % 64 == 0, name ": N %d is not a multiple of 64", p->N);                                                           \
+    SG3_REQUIRE(p->K % 32 == 0, name ": K %d is not a multiple of 32", p->K)
+
 int sg3_clip_gemm(const sg3_clip_gemm_params* p, void* stream) {
     using namespace sg3;
-    SG3_REQUIRE(p && p->a && p->w && p->out, "clip_gemm: null tensor");
-    SG3_REQUIRE(p->M > 0 && p->N > 0 && p->K > 0, "clip_gemm: sizes must be positive (M %d, N %d, K %d)", p->M, p->N, p->K);
-    SG3_REQUIRE(p->N % 64 == 0, "clip_gemm: N %d is not a multiple of 64", p->N);
-    SG3_REQUIRE(p->K % 32 == 0, "clip_gemm: K %d is not a multiple of 32", p->K);
+    SG3_CLIP_GEMM_COMMON("clip_gemm");
     SG3_REQUIRE(p->epilogue >= SG3_CLIP_EPI_F32 && p->epilogue <= SG3_CLIP_EPI_PATCH, "clip_gemm: unknown epilogue %d", p->epilogue);
     SG3_REQUIRE(aligned16(p->a) && aligned16(p->w), "clip_gemm: a and w must be 16-byte aligned");
     SG3_REQUIRE((int64_t)ceil_div(p->M, TM) <= 65535, "clip_gemm: M %d too large for one launch", p->M);
@@ -295,13 +335,47 @@ int sg3_clip_gemm(const sg3_clip_gemm_params* p, void* stream) {
         const int g = p->R / p->P;
         SG3_REQUIRE(p->M % (g * g) == 0, "clip_gemm: M %d is not a whole number of %d x %d patch grids", p->M, g, g);
     }
+    const gemm_args q = {p->a, p->w, p->bias, p->out, p->pos, p->cls, nullptr, nullptr, p->M, p->K, p->N, p->P, p->R};
     hipStream_t s = (hipStream_t)stream;
     switch (p->epilogue) {
-        case SG3_CLIP_EPI_F32:           return launch_gemm<SG3_CLIP_EPI_F32>(p, s);
-        case SG3_CLIP_EPI_F16:           return launch_gemm<SG3_CLIP_EPI_F16>(p, s);
-        case SG3_CLIP_EPI_QUICKGELU_F16: return launch_gemm<SG3_CLIP_EPI_QUICKGELU_F16>(p, s);
-        case SG3_CLIP_EPI_RESIDUAL:      return launch_gemm<SG3_CLIP_EPI_RESIDUAL>(p, s);
-        default:                         return launch_gemm<SG3_CLIP_EPI_PATCH>(p, s);
+        case SG3_CLIP_EPI_F32:           return launch_gemm<SG3_CLIP_EPI_F32>(q, s);
+        case SG3_CLIP_EPI_F16:           return launch_gemm<SG3_CLIP_EPI_F16>(q, s);
+        case SG3_CLIP_EPI_QUICKGELU_F16: return launch_gemm<SG3_CLIP_EPI_QUICKGELU_F16>(q, s);
+        case SG3_CLIP_EPI_RESIDUAL:      return launch_gemm<SG3_CLIP_EPI_RESIDUAL>(q, s);
+        default:                         return launch_gemm<SG3_CLIP_EPI_PATCH>(q, s);
+    }
+}
+
+int sg3_clip_gemm_grad(const sg3_clip_gemm_grad_params* p, void* stream) {
+    using namespace sg3;
+    SG3_CLIP_GEMM_COMMON("clip_gemm_grad");
+    const int e = p->epilogue;
+    const bool a32 = p->aF32 != 0;
+    const bool reads_aux = e == SG3_CLIP_EPI_RESIDUAL || e == SG3_CLIP_EPI_DQUICKGELU_F16, writes_aux = e == SG3_CLIP_EPI_QUICKGELU_SAVE_F16;
+    SG3_REQUIRE(e == SG3_CLIP_EPI_F32 || e == SG3_CLIP_EPI_F16 || reads_aux || writes_aux || e == SG3_CLIP_EPI_PATCH_ADJOINT, "clip_gemm_grad: unknown epilogue %d", e);
+    SG3_REQUIRE(!a32 || e == SG3_CLIP_EPI_F16 || e == SG3_CLIP_EPI_DQUICKGELU_F16 || e == SG3_CLIP_EPI_PATCH_ADJOINT,
+                "clip_gemm_grad: a float32 operand a is not built for epilogue %d", e);
+    SG3_REQUIRE((p->aux != nullptr) == (reads_aux || writes_aux), "clip_gemm_grad: epilogue %d %s", e, p->aux ? "takes no aux" : "needs aux");
+    SG3_REQUIRE(!writes_aux || (p->aux != p->out && p->aux != p->a), "clip_gemm_grad: aux must not be out or a");
+    SG3_REQUIRE(!p->scale || e == SG3_CLIP_EPI_PATCH_ADJOINT, "clip_gemm_grad: epilogue %d takes no scale", e);
+    SG3_REQUIRE(aligned16(p->a) && aligned16(p->w), "clip_gemm_grad: a and w must be 16-byte aligned");
+    SG3_REQUIRE((int64_t)ceil_div(p->M, TM) <= 65535, "clip_gemm_grad: M %d too large for one launch", p->M);
+    if (e == SG3_CLIP_EPI_PATCH_ADJOINT) {
+        SG3_REQUIRE(p->P > 0 && p->P % 8 == 0 && p->R >= p->P, "clip_gemm_grad: patch %d (a multiple of 8), resolution %d", p->P, p->R);
+        SG3_REQUIRE(p->N == 3 * p->P * p->P, "clip_gemm_grad: N %d is not 3 * patch^2", p->N);
+        SG3_REQUIRE(!p->bias, "clip_gemm_grad: the patch adjoint takes no bias");
+        const int g = p->R / p->P;
+        SG3_REQUIRE(p->M % (g * g) == 0, "clip_gemm_grad: M %d is not a whole number of %d x %d patch grids", p->M, g, g);
+    }
+    const gemm_args q = {p->a, p->w, p->bias, p->out, nullptr, nullptr, p->aux, p->scale, p->M, p->K, p->N, p->P, p->R};
+    hipStream_t s = (hipStream_t)stream;
+    switch (e) {
+        case SG3_CLIP_EPI_F32:                return launch_gemm<SG3_CLIP_EPI_F32>(q, s);
+        case SG3_CLIP_EPI_F16:                return a32 ? launch_gemm<SG3_CLIP_EPI_F16, true>(q, s) : launch_gemm<SG3_CLIP_EPI_F16>(q, s);
+        case SG3_CLIP_EPI_RESIDUAL:           return launch_gemm<SG3_CLIP_EPI_RESIDUAL>(q, s);
+        case SG3_CLIP_EPI_QUICKGELU_SAVE_F16: return launch_gemm<SG3_CLIP_EPI_QUICKGELU_SAVE_F16>(q, s);
+        case SG3_CLIP_EPI_DQUICKGELU_F16:     return a32 ? launch_gemm<SG3_CLIP_EPI_DQUICKGELU_F16, true>(q, s) : launch_gemm<SG3_CLIP_EPI_DQUICKGELU_F16>(q, s);
+        default:                              return a32 ? launch_gemm<SG3_CLIP_EPI_PATCH_ADJOINT, true>(q, s) : launch_gemm<SG3_CLIP_EPI_PATCH_ADJOINT>(q, s);
     }
 }
 

@@ -9,7 +9,9 @@ Two implementations sit behind `impl`:
            matrices and their biases in float16, LayerNorm parameters float32 and LayerNorm computed in float32, as the
            reference converts a model), and records gradients.  It is the definition.
   'hip'    torch_utils/ops/clip_transformer.py: fused HIP kernels, float16 GEMM operands with float32 accumulation, float32
-           residual stream, float32 features.  CUDA input with gradients off only.
+           residual stream, float32 features.  CUDA input; gradients off, or, for encode_image with impl='hip' given by name,
+           an image that requires a gradient while no parameter of the image tower does (the backward is HIP as well and gives
+           the gradient of the image only; it cannot be differentiated again).
 impl=None (default) takes 'hip' when the input is a CUDA tensor, gradients are off (torch.no_grad(), or no parameter and no input
 requires one) and the kernels support the tower's shape (`sg3_clip_supported`), else 'torch'.  A shape the kernels refuse is not
 an error; impl='hip' given explicitly for one is.
@@ -139,6 +141,9 @@ class CLIP(nn.Module):
             raise ValueError(f"CLIP: impl must be None, 'hip' or 'torch', got {impl!r}")
         grads = torch.is_grad_enabled() and (x.requires_grad or any(q.requires_grad for q in self.parameters()))
         ok = x.is_cuda and not grads and (ct.image_supported(self) if tower == 'visual' else ct.text_supported(self))
+        if impl == 'hip' and grads and tower == 'visual' and x.is_cuda and x.requires_grad and ct.image_supported(self) \
+                and not any(q.requires_grad for q in self.visual.parameters()):
+            return 'hip'                                         # asked for by name: the kernels' backward, gradient of the image only
         if impl == 'hip' and not ok:
             raise RuntimeError(f"CLIP: impl='hip' needs a CUDA input, gradients off and a tower shape the kernels support "
                                f"(input on {x.device}, gradients {'on' if grads else 'off'})")

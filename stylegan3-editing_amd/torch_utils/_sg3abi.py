@@ -137,6 +137,7 @@ class ClipPreprocessParams(ctypes.Structure):
 
 
 SG3_CLIP_EPI_F32, SG3_CLIP_EPI_F16, SG3_CLIP_EPI_QUICKGELU_F16, SG3_CLIP_EPI_RESIDUAL, SG3_CLIP_EPI_PATCH = 0, 1, 2, 3, 4
+SG3_CLIP_EPI_QUICKGELU_SAVE_F16, SG3_CLIP_EPI_DQUICKGELU_F16, SG3_CLIP_EPI_PATCH_ADJOINT = 5, 6, 7
 
 
 class ClipLayernormParams(ctypes.Structure):
@@ -155,6 +156,29 @@ class ClipAttentionParams(ctypes.Structure):
 
 class ClipEmbedParams(ctypes.Structure):
     _fields_ = [('tokens', c_vp), ('table', c_vp), ('pos', c_vp), ('out', c_vp), ('B', c_i32), ('L', c_i32), ('D', c_i32), ('vocab', c_i32)]
+
+
+class ClipGemmGradParams(ctypes.Structure):
+    _fields_ = [('a', c_vp), ('w', c_vp), ('bias', c_vp), ('out', c_vp), ('aux', c_vp), ('scale', c_vp),
+                ('M', c_i32), ('K', c_i32), ('N', c_i32), ('epilogue', c_i32), ('P', c_i32), ('R', c_i32), ('aF32', c_i32)]
+
+
+class ClipLayernormBwdParams(ctypes.Structure):
+    _fields_ = [('dy', c_vp), ('x', c_vp), ('gamma', c_vp), ('dx', c_vp), ('dyRowStride', c_i64), ('xRowStride', c_i64), ('dxRowStride', c_i64),
+                ('rows', c_i32), ('D', c_i32), ('accumulate', c_i32), ('eps', c_f32)]
+
+
+class ClipAttentionBwdParams(ctypes.Structure):
+    _fields_ = [('qkv', c_vp), ('dout', c_vp), ('dqkv', c_vp), ('B', c_i32), ('L', c_i32), ('heads', c_i32), ('causal', c_i32)]
+
+
+class ClipGradScaleParams(ctypes.Structure):
+    _fields_ = [('g', c_vp), ('out16', c_vp), ('inv', c_vp), ('B', c_i32), ('E', c_i32)]
+
+
+class ClipResampleParams(ctypes.Structure):
+    _fields_ = [('x', c_vp), ('xStride', c_i64 * 4), ('y', c_vp), ('yStride', c_i64 * 4),
+                ('B', c_i32), ('C', c_i32), ('H', c_i32), ('W', c_i32), ('oh', c_i32), ('ow', c_i32), ('up', c_i32), ('k', c_i32), ('adjoint', c_i32)]
 
 
 # every symbol include/sg3_ops.h declares: (name, restype, argtypes)
@@ -207,6 +231,11 @@ EXPORTS = [
     ('sg3_clip_gemm', ctypes.c_int, [ctypes.POINTER(ClipGemmParams), c_vp]),
     ('sg3_clip_attention', ctypes.c_int, [ctypes.POINTER(ClipAttentionParams), c_vp]),
     ('sg3_clip_embed', ctypes.c_int, [ctypes.POINTER(ClipEmbedParams), c_vp]),
+    ('sg3_clip_gemm_grad', ctypes.c_int, [ctypes.POINTER(ClipGemmGradParams), c_vp]),
+    ('sg3_clip_layernorm_bwd', ctypes.c_int, [ctypes.POINTER(ClipLayernormBwdParams), c_vp]),
+    ('sg3_clip_attention_bwd', ctypes.c_int, [ctypes.POINTER(ClipAttentionBwdParams), c_vp]),
+    ('sg3_clip_grad_scale', ctypes.c_int, [ctypes.POINTER(ClipGradScaleParams), c_vp]),
+    ('sg3_clip_resample', ctypes.c_int, [ctypes.POINTER(ClipResampleParams), c_vp]),
 ]
 
 _lib = None

@@ -6,6 +6,13 @@ for the stem, seven per block (LayerNorm, QKV GEMM, attention, projection GEMM +
 residual) and two for the head; between the input and the features there are only allocations and, for text, the gather of the
 end-of-text rows.  No host synchronisation, so a call can be captured in a HIP graph.
 
+`encode_image` records an autograd node when gradients are on and the image requires one (weights are frozen: the gradient is
+with respect to the image only).  The recording forward has the same launches and the same arithmetic; it keeps, per block, the
+float32 stream at the block's entry and after the attention branch, the float16 qkv and the float16 MLP pre-activation
+(22 * rows * width bytes), plus the stream before ln_pre and after the last block.  The backward is `launches_backward(layers)`
+= 7 per block + 5 launches: `layernorm_bwd`, `attention_bwd`, `grad_scale` and the data-gradient epilogues of `gemm` on
+pre-transposed float16 copies of the matrices (`PreparedTower.grad_weights`, built on the first recording call).
+
 `prepared(model, tower, device)` holds what the kernels read: the matrices in float16 in their stored [out][in] order (the two
 output projections transposed to it), everything else in float32.  The copy is keyed by the `(data_ptr, _version)` of every
 parameter of the tower and rebuilt when one changes (in-place edits bump `_version`); it is never rebuilt while a graph is being
@@ -14,10 +21,12 @@ captured, where a stale key raises.
 import ctypes
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from .. import _sg3abi as abi
 
 EPS = 1e-5
+GRAD_SCALE = True       # the per-sample power of two of the backward; False only shows what is lost without it (tests)
 
 
 def supported(width, heads, L):
@@ -52,18 +61,40 @@ def layernorm(x, gamma, beta, out, rows, D, row_stride=None, eps=EPS):
 
 
 _OUT_DTYPE = {abi.SG3_CLIP_EPI_F32: torch.float32, abi.SG3_CLIP_EPI_F16: torch.float16, abi.SG3_CLIP_EPI_QUICKGELU_F16: torch.float16,
-              abi.SG3_CLIP_EPI_RESIDUAL: torch.float32, abi.SG3_CLIP_EPI_PATCH: torch.float32}
+              abi.SG3_CLIP_EPI_RESIDUAL: torch.float32, abi.SG3_CLIP_EPI_PATCH: torch.float32, abi.SG3_CLIP_EPI_QUICKGELU_SAVE_F16: torch.float16,
+              abi.SG3_CLIP_EPI_DQUICKGELU_F16: torch.float16, abi.SG3_CLIP_EPI_PATCH_ADJOINT: torch.float32}
+_A32_OK = (abi.SG3_CLIP_EPI_F16, abi.SG3_CLIP_EPI_DQUICKGELU_F16, abi.SG3_CLIP_EPI_PATCH_ADJOINT)
 
 
-def gemm(a, w, bias, out, epilogue, M, pos=None, cls=None, patch=0, resolution=0):
+def gemm(a, w, bias, out, epilogue, M, pos=None, cls=None, patch=0, resolution=0, aux=None, scale=None):
     """out = a [M, K] . w [N, K]^T (+ bias) through `epilogue` (abi.SG3_CLIP_EPI_*); for SG3_CLIP_EPI_PATCH a is the float32 image
-    [B, 3, R, R], out the float32 token stream [B, g*g + 1, N] and M = B * g * g."""
+    [B, 3, R, R], out the float32 token stream [B, g*g + 1, N] and M = B * g * g.  `aux`: the residual to read
+    (SG3_CLIP_EPI_RESIDUAL, float32 [M, N], optional), the pre-activation to write (SG3_CLIP_EPI_QUICKGELU_SAVE_F16) or to read
+    (SG3_CLIP_EPI_DQUICKGELU_F16), float16 [M, N].  A float32 `a` is rounded to float16 by the kernel for the epilogues of
+    `_A32_OK`.  SG3_CLIP_EPI_PATCH_ADJOINT: a is the token gradient [B, g*g + 1, K], w conv1.weight transposed [3*P*P, K], out the
+    float32 image gradient [B, 3, R, R], times scale[b] when `scale` (float32 [B]) is given."""
     patchy = epilogue == abi.SG3_CLIP_EPI_PATCH
-    _need(a, torch.float32 if patchy else torch.float16, 'a'); _need(w, torch.float16, 'w'); _need(out, _OUT_DTYPE[epilogue], 'out')
+    a32 = a.dtype == torch.float32 and epilogue in _A32_OK
+    _need(a, torch.float32 if patchy or a32 else torch.float16, 'a'); _need(w, torch.float16, 'w'); _need(out, _OUT_DTYPE[epilogue], 'out')
     N, K = int(w.shape[0]), int(w.shape[1])
     if bias is not None and _need(bias, torch.float32, 'bias').numel() != N:
         raise RuntimeError(f'clip gemm: bias has {bias.numel()} entries, N is {N}')
-    if patchy:
+    if aux is not None:
+        if epilogue not in (abi.SG3_CLIP_EPI_RESIDUAL, abi.SG3_CLIP_EPI_QUICKGELU_SAVE_F16, abi.SG3_CLIP_EPI_DQUICKGELU_F16):
+            raise RuntimeError(f'clip gemm: epilogue {epilogue} takes no aux')
+        if _need(aux, torch.float32 if epilogue == abi.SG3_CLIP_EPI_RESIDUAL else torch.float16, 'aux').numel() != M * N:
+            raise RuntimeError(f'clip gemm: aux has {aux.numel()} entries, M * N is {M * N}')
+    elif epilogue in (abi.SG3_CLIP_EPI_QUICKGELU_SAVE_F16, abi.SG3_CLIP_EPI_DQUICKGELU_F16):
+        raise RuntimeError(f'clip gemm: epilogue {epilogue} needs aux')
+    if epilogue == abi.SG3_CLIP_EPI_PATCH_ADJOINT:
+        g = resolution // max(patch, 1)
+        B = M // max(g * g, 1)
+        if patch <= 0 or g <= 0 or M % (g * g) or a.numel() != B * (g * g + 1) * K or out.numel() != B * 3 * resolution * resolution or N != 3 * patch * patch \
+                or (scale is not None and _need(scale, torch.float32, 'scale').numel() != B):
+            raise RuntimeError(f'clip gemm: patch adjoint sizes do not match (M {M}, patch {patch}, resolution {resolution}, N {N}, K {K})')
+    elif scale is not None:
+        raise RuntimeError(f'clip gemm: epilogue {epilogue} takes no scale')
+    elif patchy:
         g = resolution // max(patch, 1)
         _need(pos, torch.float32, 'pos'); _need(cls, torch.float32, 'cls')
         if M % max(g * g, 1) or a.numel() != (M // max(g * g, 1)) * 3 * resolution * resolution or out.numel() != (M // max(g * g, 1)) * (g * g + 1) * N \
@@ -71,6 +102,12 @@ def gemm(a, w, bias, out, epilogue, M, pos=None, cls=None, patch=0, resolution=0
             raise RuntimeError(f'clip gemm: patch embedding sizes do not match (M {M}, patch {patch}, resolution {resolution}, N {N})')
     elif a.numel() != M * K or out.numel() != M * N:
         raise RuntimeError(f'clip gemm: sizes do not match (M {M}, K {K}, N {N}, a {a.numel()}, out {out.numel()})')
+    if aux is not None or a32 or epilogue > abi.SG3_CLIP_EPI_PATCH:          # the recording forward and the backward: sg3_clip_gemm_grad
+        p = abi.ClipGemmGradParams()
+        p.a, p.w, p.bias, p.out, p.aux, p.scale = abi.ptr(a), abi.ptr(w), abi.ptr(bias), abi.ptr(out), abi.ptr(aux), abi.ptr(scale)
+        p.M, p.K, p.N, p.epilogue, p.P, p.R, p.aF32 = int(M), K, N, int(epilogue), int(patch), int(resolution), int(a32)
+        _call(abi.load().sg3_clip_gemm_grad, p, w.device, 'sg3_clip_gemm_grad')
+        return out
     p = abi.ClipGemmParams()
     p.a, p.w, p.bias, p.out, p.pos, p.cls = abi.ptr(a), abi.ptr(w), abi.ptr(bias), abi.ptr(out), abi.ptr(pos), abi.ptr(cls)
     p.M, p.K, p.N, p.epilogue, p.P, p.R = int(M), K, N, int(epilogue), int(patch), int(resolution)
@@ -87,6 +124,43 @@ def attention(qkv, out, B, L, heads, causal):
     p.qkv, p.out, p.B, p.L, p.heads, p.causal = abi.ptr(qkv), abi.ptr(out), int(B), int(L), int(heads), int(bool(causal))
     _call(abi.load().sg3_clip_attention, p, qkv.device, 'sg3_clip_attention')
     return out
+
+
+def layernorm_bwd(dy, x, gamma, dx, rows, D, dy_stride=None, x_stride=None, dx_stride=None, accumulate=False, eps=EPS):
+    """The input gradient of LayerNorm for float32 rows (strides in elements, D by default): dx (+)= rstd (g - mean g - xhat mean(g xhat)),
+    g = gamma dy; the statistics of x are taken as `layernorm` takes them.  dx may be dy."""
+    _need(dy, torch.float32, 'dy'); _need(x, torch.float32, 'x'); _need(gamma, torch.float32, 'gamma'); _need(dx, torch.float32, 'dx')
+    sd, sx, so = (D if v is None else int(v) for v in (dy_stride, x_stride, dx_stride))
+    if gamma.numel() != D or min(sd, sx, so) < D or any(t.numel() < (rows - 1) * st + D for t, st in ((dy, sd), (x, sx), (dx, so))):
+        raise RuntimeError(f'clip layernorm_bwd: sizes do not match (rows {rows}, D {D}, strides {sd}, {sx}, {so}; dy {dy.numel()}, x {x.numel()}, dx {dx.numel()})')
+    p = abi.ClipLayernormBwdParams()
+    p.dy, p.x, p.gamma, p.dx = abi.ptr(dy), abi.ptr(x), abi.ptr(gamma), abi.ptr(dx)
+    p.dyRowStride, p.xRowStride, p.dxRowStride, p.rows, p.D, p.accumulate, p.eps = sd, sx, so, int(rows), int(D), int(bool(accumulate)), float(eps)
+    _call(abi.load().sg3_clip_layernorm_bwd, p, x.device, 'sg3_clip_layernorm_bwd')
+    return dx
+
+
+def attention_bwd(qkv, dout, dqkv, B, L, heads, causal=False):
+    """qkv float16 [B, L, 3 * 64 * heads] (as saved), dout float16 [B, L, 64 * heads] -> dqkv float16 like qkv.  Non-causal only."""
+    _need(qkv, torch.float16, 'qkv'); _need(dout, torch.float16, 'dout'); _need(dqkv, torch.float16, 'dqkv')
+    if qkv.numel() != B * L * 192 * heads or dout.numel() != B * L * 64 * heads or dqkv.numel() != qkv.numel():
+        raise RuntimeError(f'clip attention_bwd: sizes do not match (B {B}, L {L}, heads {heads}, qkv {qkv.numel()}, dout {dout.numel()}, dqkv {dqkv.numel()})')
+    p = abi.ClipAttentionBwdParams()
+    p.qkv, p.dout, p.dqkv, p.B, p.L, p.heads, p.causal = abi.ptr(qkv), abi.ptr(dout), abi.ptr(dqkv), int(B), int(L), int(heads), int(bool(causal))
+    _call(abi.load().sg3_clip_attention_bwd, p, qkv.device, 'sg3_clip_attention_bwd')
+    return dqkv
+
+
+def grad_scale(g):
+    """g float32 [B, E] -> (float16 [B, E] = g * 2^s_b, float32 [B] = 2^-s_b): per row, the power of two that puts max|g[b]| into
+    [8, 16).  Taken on the device."""
+    _need(g, torch.float32, 'g')
+    B, E = (int(v) for v in g.shape)
+    out, inv = torch.empty([B, E], dtype=torch.float16, device=g.device), torch.empty([B], dtype=torch.float32, device=g.device)
+    p = abi.ClipGradScaleParams()
+    p.g, p.out16, p.inv, p.B, p.E = abi.ptr(g), abi.ptr(out), abi.ptr(inv), B, E
+    _call(abi.load().sg3_clip_grad_scale, p, g.device, 'sg3_clip_grad_scale')
+    return out, inv
 
 
 def embed(tokens, table, pos, out):
@@ -144,6 +218,18 @@ class PreparedTower:
                                 fc=(f16(b.mlp.c_fc.weight), f32(b.mlp.c_fc.bias)), proj=(f16(b.mlp.c_proj.weight), f32(b.mlp.c_proj.bias)))
                            for b in transformer.resblocks]
         self.key = _key(model, tower, device)
+        self._grad = None
+
+    def grad_weights(self):
+        """The matrices of the image tower transposed to [in][out] float16, which makes dX = dY . W the K-contiguous GEMM: built on
+        the first recording call, kept with (and dropped with) this copy.  Never built during a graph capture."""
+        if self._grad is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError('clip encoder: the transposed weights of the backward are not prepared; run one eager forward with gradients first')
+            t = lambda w: w.t().contiguous()                    # noqa: E731
+            self._grad = dict(conv=t(self.conv), proj=t(self.proj),
+                              blocks=[{k: t(blk[k][0]) for k in ('qkv', 'out', 'fc', 'proj')} for blk in self.blocks])
+        return self._grad
 
 
 def prepared(model, tower, device):
@@ -185,6 +271,11 @@ def launches(layers, tower='visual'):
     return 7 * int(layers) + (4 if tower == 'visual' else 3)
 
 
+def launches_backward(layers):
+    """Kernel launches of the image tower's backward: scale, head GEMM and ln_post, seven per block, ln_pre and the patch adjoint."""
+    return 7 * int(layers) + 5
+
+
 def image_supported(model):
     v = model.visual
     L = (v.input_resolution // v.patch_size) ** 2 + 1
@@ -202,6 +293,8 @@ def encode_image(model, image):
     B, R, P, D = int(image.shape[0]), v.input_resolution, v.patch_size, v.width
     if image.ndim != 4 or tuple(image.shape[1:]) != (3, R, R) or B == 0:
         raise RuntimeError(f'clip encode_image: image must be [n, 3, {R}, {R}] with n > 0, got {list(image.shape)}')
+    if torch.is_grad_enabled() and image.requires_grad:
+        return _EncodeImage.apply(image, model)
     prep = prepared(model, 'visual', image.device)
     g = R // P
     L = g * g + 1
@@ -212,6 +305,82 @@ def encode_image(model, image):
     h = torch.empty([B, D], dtype=torch.float16, device=image.device)
     layernorm(x, *prep.ln_out, h, B, D, row_stride=L * D)
     return gemm(h, prep.proj, None, torch.empty([B, v.output_dim], dtype=torch.float32, device=image.device), abi.SG3_CLIP_EPI_F32, B)
+
+
+def _encode_image_recording(model, image):
+    """The forward of `encode_image` with the same launches and arithmetic, keeping what the backward reads."""
+    v = model.visual
+    B, R, P, D, heads, dev = int(image.shape[0]), v.input_resolution, v.patch_size, v.width, v.heads, image.device
+    prep = prepared(model, 'visual', dev)
+    prep.grad_weights()
+    g = R // P
+    L = g * g + 1
+    M = B * L
+    f16 = lambda *shape: torch.empty(shape, dtype=torch.float16, device=dev)          # noqa: E731
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)          # noqa: E731
+    x0 = f32(B, L, D)
+    gemm(image, prep.conv, None, x0, abi.SG3_CLIP_EPI_PATCH, B * g * g, pos=prep.pos, cls=prep.cls, patch=P, resolution=R)
+    x = layernorm(x0, *prep.ln_pre, f32(B, L, D), M, D)
+    h, att, mlp = f16(M, D), f16(M, D), f16(M, 4 * D)
+    saved = []
+    for blk in prep.blocks:
+        qkv, u, x_mid, x_out = f16(M, 3 * D), f16(M, 4 * D), f32(B, L, D), f32(B, L, D)
+        layernorm(x, *blk['ln1'], h, M, D)
+        gemm(h, *blk['qkv'], qkv, abi.SG3_CLIP_EPI_F16, M)
+        attention(qkv, att, B, L, heads, False)
+        gemm(att, *blk['out'], x_mid, abi.SG3_CLIP_EPI_RESIDUAL, M, aux=x)
+        layernorm(x_mid, *blk['ln2'], h, M, D)
+        gemm(h, *blk['fc'], mlp, abi.SG3_CLIP_EPI_QUICKGELU_SAVE_F16, M, aux=u)
+        gemm(mlp, *blk['proj'], x_out, abi.SG3_CLIP_EPI_RESIDUAL, M, aux=x_mid)
+        saved.append((x, qkv, x_mid, u))
+        x = x_out
+    hb = f16(B, D)
+    layernorm(x, *prep.ln_out, hb, B, D, row_stride=L * D)
+    feats = gemm(hb, prep.proj, None, f32(B, v.output_dim), abi.SG3_CLIP_EPI_F32, B)
+    return feats, prep, x0, saved, x
+
+
+def _encode_image_backward(prep, geom, x0, saved, x_last, dfeat):
+    """d image of sum(features * dfeat): `launches_backward` launches.  The gradient stream `gs` [B, L, D] is float32 and carries
+    the per-sample power of two of `grad_scale`, which the patch adjoint divides out."""
+    B, L, D, heads, P, R = geom
+    M, dev, gw = B * L, dfeat.device, prep.grad_weights()
+    f16 = lambda *shape: torch.empty(shape, dtype=torch.float16, device=dev)          # noqa: E731
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)          # noqa: E731
+    g16, inv = grad_scale(dfeat) if GRAD_SCALE else (dfeat.half(), None)
+    dh = gemm(g16, gw['proj'], None, f32(B, D), abi.SG3_CLIP_EPI_F32, B)
+    gs = torch.zeros([B, L, D], dtype=torch.float32, device=dev)
+    layernorm_bwd(dh, x_last, prep.ln_out[0], gs, B, D, x_stride=L * D, dx_stride=L * D)
+    du, dn, datt, dqkv = f16(M, 4 * D), f32(M, D), f16(M, D), f16(M, 3 * D)
+    for blk, wt, (x_in, qkv, x_mid, u) in zip(reversed(prep.blocks), reversed(gw['blocks']), reversed(saved)):
+        gemm(gs, wt['proj'], None, du, abi.SG3_CLIP_EPI_DQUICKGELU_F16, M, aux=u)
+        gemm(du, wt['fc'], None, dn, abi.SG3_CLIP_EPI_F32, M)
+        layernorm_bwd(dn, x_mid, blk['ln2'][0], gs, M, D, accumulate=True)
+        gemm(gs, wt['out'], None, datt, abi.SG3_CLIP_EPI_F16, M)
+        attention_bwd(qkv, datt, dqkv, B, L, heads)
+        gemm(dqkv, wt['qkv'], None, dn, abi.SG3_CLIP_EPI_F32, M)
+        layernorm_bwd(dn, x_in, blk['ln1'][0], gs, M, D, accumulate=True)
+    layernorm_bwd(gs, x0, prep.ln_pre[0], gs, M, D)
+    g = R // P
+    dimage = (torch.zeros if R % P else torch.empty)([B, 3, R, R], dtype=torch.float32, device=dev)      # pixels past the patch grid feed nothing
+    return gemm(gs, gw['conv'], None, dimage, abi.SG3_CLIP_EPI_PATCH_ADJOINT, B * g * g, patch=P, resolution=R, scale=inv)
+
+
+class _EncodeImage(torch.autograd.Function):
+    """encode_image with the gradient with respect to the image (weights frozen)."""
+
+    @staticmethod
+    def forward(ctx, image, model):
+        v = model.visual
+        feats, prep, x0, saved, x_last = _encode_image_recording(model, image)
+        ctx.prep, ctx.x0, ctx.saved, ctx.x_last = prep, x0, saved, x_last
+        ctx.geom = (int(image.shape[0]), int(x0.shape[1]), v.width, v.heads, v.patch_size, v.input_resolution)
+        return feats
+
+    @staticmethod
+    @once_differentiable                # double backward raises ("differentiate twice"): impl='torch' is the differentiable composite
+    def backward(ctx, dfeat):
+        return _encode_image_backward(ctx.prep, ctx.geom, ctx.x0, ctx.saved, ctx.x_last, dfeat.float().contiguous()), None
 
 
 def encode_text(model, tokens):
