@@ -713,6 +713,92 @@ typedef struct sg3_latent_mapper_params {
 SG3_API int sg3_latent_mapper(const sg3_latent_mapper_params* p, void* stream);
 
 /* ----------------------------------------------------------------------
+ * StyleCLIP latent mapper for training: the forward above with every activation kept, and its backward.
+ *
+ * sg3_latent_mapper_train_forward: the same two kernels, in the same order, as sg3_latent_mapper (so delta and out are bitwise
+ *   equal to its results), writing h0..h3 into the caller's acts [4][N][L][D] and h4 into delta (required here) instead of a
+ *   ping-pong scratch.  acts rows of levels in no group are not written.  Five launches (one when groups == 0).
+ *
+ * sg3_latent_mapper_backward: given dDelta and / or dOut (either may be NULL, not both when groups > 0; dOut adds alpha * dOut
+ *   to dDelta and passes straight through to dx), with dz_i = dh_i * (h_i > 0 ? sqrt(2) : 0.2 * sqrt(2)) taken from the saved h_i:
+ *     dh_(i-1) = dz_i @ weight[g][i-1]                                     i = 4..1   (fp32 MFMA, fixed order, batch invariant)
+ *     dW[g][i-1] = (dz_i^T @ h_(i-1)) * wScale[4g+i-1]                     gradient of the STORED weight  [D][D]
+ *     dB[g][i-1] = (sum over rows of dz_i) * bScale[4g+i-1]                gradient of the STORED bias    [D]
+ *     dx[n,l,:]  = r * dh0_l - x_l * r^3 * (1/Lg) * sum_j dh0_j * x_j  (+ dOut[n,l,:])   over the group's levels,
+ *   and dx = dOut (zero when NULL) on levels in no group.  dx may be NULL (then the last data gradient and the PixelNorm backward
+ *   are skipped); dW and dB are both given or both NULL (then no weight gradient is launched).  x, acts, delta are what the
+ *   forward read and wrote.  scratch: 2 * N * L * D floats.  At most ten launches: dz_4, 4 x data gradient, 4 x weight gradient,
+ *   PixelNorm; every result is a fixed sequence of operations (no atomics), so two runs are bitwise equal.
+ *   weight, acts, delta, scratch, dDelta 16-byte aligned; every written buffer overlaps no other; D == 512, L <= 32.
+ * ---------------------------------------------------------------------- */
+typedef struct sg3_latent_mapper_train_params {
+    const float*   x;              /* [N][L][D] */
+    const float*   weight;         /* [groups][4][D][D] */
+    const float*   bias;           /* [groups][4][D] */
+    float*         out;            /* [N][L][D] or NULL */
+    float*         delta;          /* [N][L][D]  (h4) */
+    float*         acts;           /* [4][N][L][D]  (h0..h3) */
+    int32_t        N, L, D;
+    int32_t        groups;
+    int32_t        levelBegin[4];
+    int32_t        levelEnd[4];
+    float          alpha;
+} sg3_latent_mapper_train_params;
+
+typedef struct sg3_latent_mapper_backward_params {
+    const float*   x;              /* [N][L][D] */
+    const float*   weight;         /* [groups][4][D][D]  prepared, as in the forward */
+    const float*   acts;           /* [4][N][L][D] */
+    const float*   delta;          /* [N][L][D] */
+    const float*   dDelta;         /* [N][L][D] or NULL */
+    const float*   dOut;           /* [N][L][D] or NULL */
+    float*         dx;             /* [N][L][D] or NULL */
+    float*         dW;             /* [groups][4][D][D] or NULL */
+    float*         dB;             /* [groups][4][D] or NULL */
+    float*         scratch;        /* 2 * N * L * D floats */
+    int32_t        N, L, D;
+    int32_t        groups;
+    int32_t        levelBegin[4];
+    int32_t        levelEnd[4];
+    float          alpha;
+    float          wScale[16];     /* [groups][4]  EqualLinear.scale */
+    float          bScale[16];     /* [groups][4]  EqualLinear.lr_mul */
+} sg3_latent_mapper_backward_params;
+
+SG3_API int sg3_latent_mapper_train_forward(const sg3_latent_mapper_train_params* p, void* stream);
+SG3_API int sg3_latent_mapper_backward(const sg3_latent_mapper_backward_params* p, void* stream);
+
+/* ----------------------------------------------------------------------
+ * One Ranger step (RAdam + lookahead + gradient centralisation, reference utils/ranger.py:79-165) of up to 32 dense float32
+ * tensors in one launch; one workgroup per row, a 1-D tensor is one row.  Per element, each line rounded as the torch op it restates:
+ *     g = grad - mean(row)                 when centralise (written back to grad; the row sum has a fixed order)
+ *     expAvgSq = expAvgSq * beta2 + oneMinusBeta2 * g * g;      expAvg = expAvg * beta1 + oneMinusBeta1 * g
+ *     p = p - decay * p                    when decay (= weight_decay * lr) != 0
+ *     p = p - stepLr * expAvg / (sqrt(expAvgSq) + eps)   when adaptive, else   p = p - stepLr * expAvg      (stepLr = step_size * lr)
+ *     slow = slow + alpha * (p - slow);  p = slow        when lookahead
+ * step_size, adaptive and lookahead come from the host's step count.  No buffer of the call may overlap another.
+ * ---------------------------------------------------------------------- */
+typedef struct sg3_ranger_tensor {
+    float*         p;
+    float*         grad;
+    float*         expAvg;
+    float*         expAvgSq;
+    float*         slow;
+    int32_t        rows, cols;
+    int32_t        centralise;
+    int32_t        reserved;
+} sg3_ranger_tensor;
+
+typedef struct sg3_ranger_params {
+    sg3_ranger_tensor t[32];
+    int32_t        count;
+    float          beta1, beta2, oneMinusBeta1, oneMinusBeta2, eps, decay, stepLr, alpha;
+    int32_t        adaptive, lookahead;
+} sg3_ranger_params;
+
+SG3_API int sg3_ranger_step(const sg3_ranger_params* p, void* stream);
+
+/* ----------------------------------------------------------------------
  * CLIP image preprocessing of the StyleCLIP delta_i_c sweep (reference
  * editing/styleclip_global_directions/preprocess/create_delta_i_c.py:53-56), for x [B,3,H,W] float32:
  *     y = F.interpolate(x, size=(h, w), mode='bicubic', align_corners=True)

@@ -7,7 +7,10 @@ level group -- coarse 0-4 (`course_mapping`, the reference's spelling), medium 5
 
 In eval mode, with no gradient recorded, on a CUDA float32 [N, 16, 512] input and 512 x 512 weights, `SingleMapper.forward` and
 `LevelsMapper.forward` run every group in one fused HIP forward (torch_utils/ops/latent_mapper.py, csrc/sg3_latent_mapper.hip);
-`edit(w, alpha)` returns `w + alpha * mapper(w)` from the same launches.  Anywhere else the composite runs.
+`edit(w, alpha)` returns `w + alpha * mapper(w)` from the same launches.  In TRAINING mode with gradients enabled, on the same
+inputs, both run the differentiable HIP form (`latent_mapper.train_forward`: the same forward kernels with the activations kept,
+and a HIP backward to the input and to every weight and bias).  Anywhere else -- eval mode with gradients enabled included, which
+the tests use as their fp32 yardstick -- the composite runs.
 """
 import torch
 from torch import nn
@@ -64,6 +67,12 @@ class _FusedMapperMixin:
     def _fused_ok(self, x):
         if self.training or torch.is_grad_enabled():
             return False
+        return self._fused_shapes_ok(x)
+
+    def _fused_train_ok(self, x):
+        return self.training and torch.is_grad_enabled() and self._fused_shapes_ok(x)
+
+    def _fused_shapes_ok(self, x):
         if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[1] == 16 and x.shape[2] == 512):
             return False
         for _, m in self._groups():
@@ -80,10 +89,18 @@ class _FusedMapperMixin:
         prep = latent_mapper.prepared(self, [m for _, m in on], x.device)
         return latent_mapper.launch(x, prep, [r for r, _ in on], alpha=alpha, want_out=want_out, want_delta=want_delta)
 
+    def _fused_train(self, x, alpha, want_out):
+        """(out, delta) with gradients to x and the parameters; out is None unless want_out."""
+        from torch_utils.ops import latent_mapper
+        on = [(r, m) for r, m in self._groups() if m is not None]
+        return latent_mapper.train_forward(x, self, [m for _, m in on], [r for r, _ in on], alpha=alpha, want_out=want_out)
+
     def edit(self, w, alpha=0.1):
         """w + alpha * self(w) (reference scripts/inference.py:98); on the HIP path straight from the kernel."""
         if self._fused_ok(w):
             return self._fused(w, alpha, True, False)[0]
+        if self._fused_train_ok(w):
+            return self._fused_train(w, alpha, True)[0]
         return w + alpha * self(w)
 
 
@@ -99,6 +116,8 @@ class SingleMapper(_FusedMapperMixin, Module):
     def forward(self, x):
         if self._fused_ok(x):
             return self._fused(x, 0.1, False, True)[1]
+        if self._fused_train_ok(x):
+            return self._fused_train(x, 0.1, False)[1]
         return self.mapping(x)
 
 
@@ -121,6 +140,8 @@ class LevelsMapper(_FusedMapperMixin, Module):
     def forward(self, x):
         if self._fused_ok(x):
             return self._fused(x, 0.1, False, True)[1]
+        if self._fused_train_ok(x):
+            return self._fused_train(x, 0.1, False)[1]
         parts = []
         for (b, e), m in self._groups():
             xs = x[:, b:e, :] if e < 16 else x[:, b:, :]

@@ -131,6 +131,30 @@ class LatentMapperParams(ctypes.Structure):
                 ('alpha', c_f32)]
 
 
+class LatentMapperTrainParams(ctypes.Structure):
+    _fields_ = [('x', c_vp), ('weight', c_vp), ('bias', c_vp), ('out', c_vp), ('delta', c_vp), ('acts', c_vp),
+                ('N', c_i32), ('L', c_i32), ('D', c_i32), ('groups', c_i32), ('levelBegin', c_i32 * 4), ('levelEnd', c_i32 * 4),
+                ('alpha', c_f32)]
+
+
+class LatentMapperBackwardParams(ctypes.Structure):
+    _fields_ = [('x', c_vp), ('weight', c_vp), ('acts', c_vp), ('delta', c_vp), ('dDelta', c_vp), ('dOut', c_vp),
+                ('dx', c_vp), ('dW', c_vp), ('dB', c_vp), ('scratch', c_vp),
+                ('N', c_i32), ('L', c_i32), ('D', c_i32), ('groups', c_i32), ('levelBegin', c_i32 * 4), ('levelEnd', c_i32 * 4),
+                ('alpha', c_f32), ('wScale', c_f32 * 16), ('bScale', c_f32 * 16)]
+
+
+class RangerTensor(ctypes.Structure):
+    _fields_ = [('p', c_vp), ('grad', c_vp), ('expAvg', c_vp), ('expAvgSq', c_vp), ('slow', c_vp),
+                ('rows', c_i32), ('cols', c_i32), ('centralise', c_i32), ('reserved', c_i32)]
+
+
+class RangerParams(ctypes.Structure):
+    _fields_ = [('t', RangerTensor * 32), ('count', c_i32),
+                ('beta1', c_f32), ('beta2', c_f32), ('oneMinusBeta1', c_f32), ('oneMinusBeta2', c_f32), ('eps', c_f32), ('decay', c_f32),
+                ('stepLr', c_f32), ('alpha', c_f32), ('adaptive', c_i32), ('lookahead', c_i32)]
+
+
 class ClipPreprocessParams(ctypes.Structure):
     _fields_ = [('x', c_vp), ('xStride', c_i64 * 4), ('y', c_vp), ('yStride', c_i64 * 4),
                 ('B', c_i32), ('C', c_i32), ('H', c_i32), ('W', c_i32), ('h', c_i32), ('w', c_i32), ('mean', c_f32 * 3), ('std', c_f32 * 3)]
@@ -225,6 +249,9 @@ EXPORTS = [
     ('sg3_resample_coeffs', ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, c_vp, c_vp]),
     ('sg3_image_finish', ctypes.c_int, [ctypes.POINTER(ImageFinishParams), c_vp]),
     ('sg3_latent_mapper', ctypes.c_int, [ctypes.POINTER(LatentMapperParams), c_vp]),
+    ('sg3_latent_mapper_train_forward', ctypes.c_int, [ctypes.POINTER(LatentMapperTrainParams), c_vp]),
+    ('sg3_latent_mapper_backward', ctypes.c_int, [ctypes.POINTER(LatentMapperBackwardParams), c_vp]),
+    ('sg3_ranger_step', ctypes.c_int, [ctypes.POINTER(RangerParams), c_vp]),
     ('sg3_clip_preprocess', ctypes.c_int, [ctypes.POINTER(ClipPreprocessParams), c_vp]),
     ('sg3_clip_supported', ctypes.c_int, [ctypes.c_int] * 3),
     ('sg3_clip_layernorm', ctypes.c_int, [ctypes.POINTER(ClipLayernormParams), c_vp]),
