@@ -1006,6 +1006,73 @@ typedef struct sg3_clip_resample_params {
 
 SG3_API int sg3_clip_resample(const sg3_clip_resample_params* p, void* stream);
 
+/* ----------------------------------------------------------------------
+ * Image preparation of the identity loss (reference criteria/id_loss.py extract_feats): AdaptiveAvgPool2d(256) when H != 256,
+ * crop [35:223, 32:220], AdaptiveAvgPool2d(112) -- one separable banded linear map per plane, out = Ay X Ax^T, as one launch that
+ * reads the source once and writes no intermediate.  adjoint != 0 runs the transpose in gather form: x is then the OUTPUT
+ * [B][C][H][W] (exact zeros outside the crop's footprint, no atomics) and y the INPUT [B][C][112][112].
+ * float32, strides in elements (n, c, y, x), any layout; the written tensor must not overlap the read one.
+ * `pool` must be 1 exactly when H != 256 (the reference's rule; the columns follow the rows); an unpooled image needs W >= 220.
+ * ---------------------------------------------------------------------- */
+typedef struct sg3_face_pool_params {
+    float*         x;              /* [B][C][H][W]: read (forward) or written (adjoint) */
+    int64_t        xStride[4];
+    float*         y;              /* [B][C][112][112]: written (forward) or read (adjoint) */
+    int64_t        yStride[4];
+    int32_t        B, C, H, W;
+    int32_t        pool;
+    int32_t        adjoint;
+} sg3_face_pool_params;
+
+SG3_API int sg3_face_pool(const sg3_face_pool_params* p, void* stream);
+
+/* ----------------------------------------------------------------------
+ * Data gradient of sg3_conv2d's convolutions (k in {1, 3}, stride in {1, 2}, padding k / 2) on the fp32 matrix cores:
+ *     dx[n][i][y][x] = sum_{o,ky,kx} w[o][i][ky][kx] dy[n][o][(y + pad - ky) / stride][(x + pad - kx) / stride]   (taps that divide)
+ * Stride 2 runs as four dense sub-convolutions, one per pixel parity, over the 1, 2, 2 and 4 taps that reach it.
+ * wPacked: sg3_conv2d_pack(wT, outScale, ..., O = I, I = O, k, SG3_CONV_FP32) of the TRANSPOSED weight wT[i][o][ky][kx] (not
+ * flipped); its outScale is then a per-input-channel scale of dx (a BatchNorm in front of the forward convolution).
+ * H x W is the size of dx (a stride-2 output size does not determine it); OH x OW that of dy and must be the forward's output size.
+ * Epilogue per element, in this order:  v = acc;  v += addend[n sN + i sC + y sH + x sW] (addend != NULL);
+ * v *= (act[n][i][y][x] > 0 ? 1 : slope[i]) (act != NULL: the PReLU whose output -- or pre-activation, when a slope is negative --
+ * was saved as act, contiguous like dx).  dy and dx are contiguous float32 and must not overlap.
+ * ---------------------------------------------------------------------- */
+typedef struct sg3_conv2d_dgrad_params {
+    const float*   dy;             /* [N][O][OH][OW] */
+    const float*   wPacked;
+    float*         dx;             /* [N][I][H][W] */
+    const float*   act;            /* [N][I][H][W] or NULL */
+    const float*   slope;          /* [I], required with act */
+    const float*   addend;         /* or NULL */
+    int64_t        addStride[4];
+    int32_t        N, I, O, H, W, OH, OW;
+    int32_t        k, stride;
+} sg3_conv2d_dgrad_params;
+
+SG3_API int sg3_conv2d_dgrad(const sg3_conv2d_dgrad_params* p, void* stream);
+
+/* ----------------------------------------------------------------------
+ * Backward of sg3_se_residual (out = shortcut + res * sigmoid(fc2 relu(fc1 mean_hw(res)))), two launches:
+ *     dg = sum_hw dout res;  dz = dg g (1 - g);  dh = fc2^T dz;  du = dh [u > 0];  dm = fc1^T du;  dres = dout g + dm / (H W)
+ * `res` is the forward's res input and `mean` what the forward left in its `mean`.  The shortcut's gradient is dout itself and is
+ * not written; with dscatter != NULL (identity shortcut of a stride-2 unit) dscatter [N][C][inH][inW] receives dout at the even
+ * positions and zero elsewhere, H = ceil(inH / 2), W = ceil(inW / 2).  All tensors contiguous float32; dg [N][C] is scratch.
+ * ---------------------------------------------------------------------- */
+typedef struct sg3_se_bwd_params {
+    const float*   dout;           /* [N][C][H][W] */
+    const float*   res;            /* [N][C][H][W] */
+    const float*   mean;           /* [N][C] */
+    const float*   fc1;            /* [R][C] */
+    const float*   fc2;            /* [C][R] */
+    float*         dg;             /* [N][C] scratch */
+    float*         dres;           /* [N][C][H][W] */
+    float*         dscatter;       /* [N][C][inH][inW] or NULL */
+    int32_t        N, C, H, W, R;
+    int32_t        inH, inW;
+} sg3_se_bwd_params;
+
+SG3_API int sg3_se_residual_bwd(const sg3_se_bwd_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

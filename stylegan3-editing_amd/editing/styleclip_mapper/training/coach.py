@@ -15,9 +15,10 @@ What differs from the reference:
   logging   Scalars go to `logs/metrics.jsonl`, one JSON object per logged step and prefix, and to a tensorboard SummaryWriter
             only if that is importable.  Image grids (inputs above, edits below) are finished by
             torch_utils.ops.image_finish.to_uint8 and written with PIL; torchvision is not needed.
-  ID loss   The IR-SE50 identity loss is not part of this package.  `Coach(opts, id_loss=module)` takes a module with the
-            reference's call, `loss, sim_improvement, logs = id_loss(x_hat, x, x)`; with `opts.id_lambda > 0` and no module a
-            NotImplementedError says so (pass --id_lambda 0).  The default of 0.06 is the reference's.
+  ID loss   With `opts.id_lambda > 0` (the reference's default is 0.06) the loss is `criteria.id_loss.IDLoss(opts)` when
+            `opts.ir_se50_weights` names an existing file, or a module given as `Coach(opts, id_loss=module)` with the reference's
+            call, `loss, sim_improvement, logs = id_loss(x_hat, x, x)`.  With neither, a NotImplementedError says so (the weights
+            are no part of this package: pass --ir_se50_weights, a module, or --id_lambda 0).
   scalars   `float(loss)` waits for the device, so `calc_loss` returns tensors and they are read only on steps that log,
             validate or write a checkpoint.
   device    `opts.device` when set, else cuda:0 when there is one.  `net` and `clip_loss` may be passed ready-made.
@@ -48,8 +49,12 @@ class Coach:
         self.opts.device = self.device
 
         if self.opts.id_lambda > 0 and id_loss is None:
-            raise NotImplementedError('the IR-SE50 ID loss is not part of this package: pass an id_loss module to Coach, or train '
-                                      'with --id_lambda 0')
+            weights = getattr(opts, 'ir_se50_weights', None)
+            if not (weights and os.path.isfile(weights)):
+                raise NotImplementedError('the IR-SE50 ID loss is not part of this package: pass an id_loss module to Coach, or train '
+                                          'with --id_lambda 0')
+            from criteria.id_loss import IDLoss
+            id_loss = IDLoss(opts)
         if net is None:
             from editing.styleclip_mapper.styleclip_mapper import StyleCLIPMapper
             net = StyleCLIPMapper(self.opts)

@@ -118,6 +118,82 @@ class _ResidualUnit(Module):
             return torch.addcmul(shortcut, res, se.gate(res))
         return res + shortcut
 
+    # ---- the same path differentiated with respect to the input (frozen weights: the identity loss) ----
+    def _grad_pack(self):
+        """Transposed weights for the data gradient (torch_utils/ops/plain_conv_grad.py), kept inside `_packed` so that whatever
+        invalidates the forward pack drops these too.  BN2 and the shortcut's BatchNorm scale dy's channels, BN1 the result's."""
+        if self._packed is None:
+            self._pack()
+        pk = self._packed
+        if 'grad' not in pk:
+            from torch_utils.ops.plain_conv import ACT_NONE, PackedConv, bn_affine
+            from torch_utils.ops.plain_conv_grad import PackedDgrad
+            bn1, conv1, prelu, conv2, bn2 = (self.res_layer[i] for i in range(5))
+            a1, b1 = bn_affine(bn1)
+            a2, _ = bn_affine(bn2)
+            gk = dict(conv1=PackedDgrad(conv1.weight, out_scale=a1, stride=1), conv2=PackedDgrad(conv2.weight, k_scale=a2, stride=self.stride))
+            if isinstance(self.shortcut_layer, Sequential):
+                a, _ = bn_affine(self.shortcut_layer[1])
+                gk['shortcut'] = PackedDgrad(self.shortcut_layer[0].weight, k_scale=a, stride=self.stride)
+            # A PReLU output tells the branch its input took only while no slope is negative (decided here, once per pack); a layer
+            # with a negative slope keeps its pre-activation instead: conv1 without the epilogue, then one PReLU
+            gk['mixed'] = bool((prelu.weight.detach() < 0).any())
+            if gk['mixed']:
+                gk['conv1_linear'] = PackedConv(conv1.weight, in_scale=a1, in_shift=b1, act=ACT_NONE, stride=1, padding=1)
+            gk['slope'] = prelu.weight.detach().to(torch.float32).contiguous()
+            pk['grad'] = gk
+        return pk['grad']
+
+    def forward_hip_record(self, x):
+        """`forward_hip` keeping what `backward_hip` needs (the packed gradient weights included, so that a repack between forward
+        and backward cannot change them) -> (out, saved).  At most four launches, five with a projection."""
+        gk = self._grad_pack()
+        pk = self._packed
+        if gk['mixed']:
+            act = gk['conv1_linear'](x)
+            h1 = torch.nn.functional.prelu(act, gk['slope'])
+        else:
+            act = h1 = pk['conv1'](x)
+        res = pk['conv2'](h1)
+        if 'shortcut' in pk:
+            shortcut = pk['shortcut'](x)
+        else:
+            shortcut = x if self.stride == 1 else x[:, :, ::self.stride, ::self.stride]
+        mean = None
+        if self.use_se:
+            from torch_utils.ops import se_ops
+            se = self.res_layer[5]
+            out, mean = se_ops.se_residual_record(res, shortcut, se.fc1.weight, se.fc2.weight)
+        else:
+            out = res + shortcut
+        return out, (act, res, mean, (int(x.shape[2]), int(x.shape[3])), gk)
+
+    def backward_hip(self, saved, dout, post=None):
+        """Gradient of `forward_hip_record` with respect to x:
+            dx = a1 * dgrad1(prelu' * dgrad2(dres; a2 w2, stride)) + shortcut path,   dres from the SE backward (or dout itself).
+        `post` = (act, slope) multiplies dx by the derivative of a PReLU in front of the unit (the stem's).  At most six launches,
+        seven with a projection."""
+        act, res, mean, (h, w), gk = saved                   # gk: the transposed weights the forward's pack belongs to
+        identity_s2 = 'shortcut' not in gk and self.stride != 1
+        dsc = None
+        if self.use_se:
+            from torch_utils.ops import se_ops
+            se = self.res_layer[5]
+            dres, dsc = se_ops.se_residual_bwd(dout, res, mean, se.fc1.weight, se.fc2.weight, scatter_hw=(h, w) if identity_s2 else None)
+        else:
+            dres = dout
+            if identity_s2:
+                dsc = dout.new_zeros([dout.shape[0], dout.shape[1], h, w])
+                dsc[:, :, ::self.stride, ::self.stride] = dout
+        dh1 = gk['conv2'].run(dres, (h, w), act=act, slope=gk['slope'])
+        if 'shortcut' in gk:
+            addend = gk['shortcut'].run(dout, (h, w))
+        else:
+            addend = dsc if identity_s2 else dout
+        if post is None:
+            return gk['conv1'].run(dh1, (h, w), addend=addend)
+        return gk['conv1'].run(dh1, (h, w), addend=addend, act=post[0], slope=post[1])
+
 
 class bottleneck_IR(_ResidualUnit):  # noqa: N801  (reference class name)
     use_se = False

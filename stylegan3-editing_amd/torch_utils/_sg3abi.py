@@ -205,6 +205,21 @@ class ClipResampleParams(ctypes.Structure):
                 ('B', c_i32), ('C', c_i32), ('H', c_i32), ('W', c_i32), ('oh', c_i32), ('ow', c_i32), ('up', c_i32), ('k', c_i32), ('adjoint', c_i32)]
 
 
+class FacePoolParams(ctypes.Structure):
+    _fields_ = [('x', c_vp), ('xStride', c_i64 * 4), ('y', c_vp), ('yStride', c_i64 * 4),
+                ('B', c_i32), ('C', c_i32), ('H', c_i32), ('W', c_i32), ('pool', c_i32), ('adjoint', c_i32)]
+
+
+class Conv2dDgradParams(ctypes.Structure):
+    _fields_ = [('dy', c_vp), ('wPacked', c_vp), ('dx', c_vp), ('act', c_vp), ('slope', c_vp), ('addend', c_vp), ('addStride', c_i64 * 4),
+                ('N', c_i32), ('I', c_i32), ('O', c_i32), ('H', c_i32), ('W', c_i32), ('OH', c_i32), ('OW', c_i32), ('k', c_i32), ('stride', c_i32)]
+
+
+class SeBwdParams(ctypes.Structure):
+    _fields_ = [('dout', c_vp), ('res', c_vp), ('mean', c_vp), ('fc1', c_vp), ('fc2', c_vp), ('dg', c_vp), ('dres', c_vp), ('dscatter', c_vp),
+                ('N', c_i32), ('C', c_i32), ('H', c_i32), ('W', c_i32), ('R', c_i32), ('inH', c_i32), ('inW', c_i32)]
+
+
 # every symbol include/sg3_ops.h declares: (name, restype, argtypes)
 EXPORTS = [
     ('sg3_abi_version', ctypes.c_int, []),
@@ -263,6 +278,9 @@ EXPORTS = [
     ('sg3_clip_attention_bwd', ctypes.c_int, [ctypes.POINTER(ClipAttentionBwdParams), c_vp]),
     ('sg3_clip_grad_scale', ctypes.c_int, [ctypes.POINTER(ClipGradScaleParams), c_vp]),
     ('sg3_clip_resample', ctypes.c_int, [ctypes.POINTER(ClipResampleParams), c_vp]),
+    ('sg3_face_pool', ctypes.c_int, [ctypes.POINTER(FacePoolParams), c_vp]),
+    ('sg3_conv2d_dgrad', ctypes.c_int, [ctypes.POINTER(Conv2dDgradParams), c_vp]),
+    ('sg3_se_residual_bwd', ctypes.c_int, [ctypes.POINTER(SeBwdParams), c_vp]),
 ]
 
 _lib = None
