@@ -28,6 +28,18 @@ void set_error(const char* fmt, ...);
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// CUs of the current device, read once per device; 256 without one
+inline int device_cu_count() {
+    static int cus[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    if (cus[dev] == 0) {
+        int n = 0;
+        cus[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
+    }
+    return cus[dev];
+}
+
 // floor division / modulus for possibly negative numerators (device + host)
 __host__ __device__ static inline int floor_div(int a, int b) {
     int q = a / b; int r = a - q * b; return (r != 0 && ((r < 0) != (b < 0))) ? q - 1 : q;

@@ -8,13 +8,10 @@
 // global->registers during the MFMA loop.  Differences: stride 1 or 2; a per-input-channel affine (the BatchNorm that
 // precedes the first convolution of a bottleneck) applied while staging, only inside the image so zero padding stays
 // zero; epilogue bias (folded BatchNorm / conv bias) and PReLU / leaky ReLU.
-#include "sg3_common.h"
+#include "sg3_igemm_f32.h"
 #include "sg3_split.h"
 
 namespace sg3 {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct PlainConvParams {
     const float* x; const float* wp; const float* inScale; const float* inShift; const float* bias; const float* slope; float* out;
@@ -26,7 +23,7 @@ struct PlainConvParams {
 template <int KS, int STRIDE, int WM, int WN, int TM, int TN>
 __global__ void __launch_bounds__(256)
 conv2d_mfma_kernel(PlainConvParams p) {
-    constexpr int TAPS = KS * KS, KC = (KS == 3) ? 8 : 16;
+    constexpr int TAPS = ConvK<KS>::TAPS, KC = ConvK<KS>::KC;
     constexpr int BM = WM * TM * 32;
     constexpr int ROWS = WN * TN;
     constexpr int PH = (ROWS - 1) * STRIDE + KS, PW = 31 * STRIDE + KS;
@@ -47,11 +44,7 @@ conv2d_mfma_kernel(PlainConvParams p) {
     const int wm = wave / WN, wn = wave % WN;
     const int li = lane & 31, lh = lane >> 5;
 
-    int bid = blockIdx.x;
-    {
-        const int nb = p.totalBlocks, q = nb >> 3, r = nb & 7, xcd = bid & 7, k = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-    }
+    int bid = xcd_block(blockIdx.x, p.totalBlocks);
     const int mt = bid % p.mTiles; bid /= p.mTiles;
     const int xt = bid % p.xTiles; bid /= p.xTiles;
     const int yt = bid % p.yTiles; const int n = bid / p.yTiles;
@@ -219,11 +212,7 @@ conv2d_f16x3_kernel(PlainConvParams p, int* flag) {
     const int wm = wave / WN, wn = wave % WN;
     const int li = lane & 31, lh = lane >> 5;
 
-    int bid = blockIdx.x;
-    {
-        const int nb = p.totalBlocks, q = nb >> 3, r = nb & 7, xcd = bid & 7, k = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-    }
+    int bid = xcd_block(blockIdx.x, p.totalBlocks);
     const int mt = bid % p.mTiles; bid /= p.mTiles;
     const int xt = bid % p.xTiles; bid /= p.xTiles;
     const int yt = bid % p.yTiles; const int n = bid / p.yTiles;
@@ -398,7 +387,7 @@ conv2d_f16x3_kernel(PlainConvParams p, int* flag) {
             float bv[16], sl[16], ws[16];
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                const int o = min(oL + (r & 3) + 8 * (r >> 2), p.O - 1);                // channels beyond O are dropped by the store
+                const int o = min(oL + mfma_c_row(r), p.O - 1);                // channels beyond O are dropped by the store
                 bv[r] = p.bias ? p.bias[o] : 0.f;
                 ws[r] = p.wScale[o];
                 sl[r] = p.act == 1 ? p.slope[o] : (p.act == 2 ? p.slope[0] : 1.f);
@@ -413,7 +402,7 @@ conv2d_f16x3_kernel(PlainConvParams p, int* flag) {
                 for (int r = 0; r < 16; r++) {
                     float v = acc[a][b][r] * ws[r] + bv[r];
                     if (p.act) v = v < 0.f ? v * sl[r] : v;
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), orr, (int)(rowOff + (unsigned)((r & 3) + 8 * (r >> 2)) * planeB), 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), orr, (int)(rowOff + (unsigned)mfma_c_row(r) * planeB), 0, 0);
                 }
             }
         }
@@ -423,7 +412,7 @@ conv2d_f16x3_kernel(PlainConvParams p, int* flag) {
     for (int a = 0; a < TM; a++)
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-            const int o = o0 + (wm * TM + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            const int o = o0 + (wm * TM + a) * 32 + mfma_c_row(r) + 4 * lh;
             if (o >= p.O) continue;
             const float bv = p.bias ? p.bias[o] : 0.f;
             const float sl = p.act == 1 ? p.slope[o] : (p.act == 2 ? p.slope[0] : 1.f);
@@ -468,16 +457,18 @@ conv2d_pack_f16x3_kernel(const float* w, const float* outScale, float* wp, float
     }
 }
 
-// CUs of the current device, read once per device
-static int device_cu_count() {
-    static int cus[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (cus[dev] == 0) {
-        int n = 0;
-        cus[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-    }
-    return cus[dev];
+// The kernel parameters of a call on BM-channel x (ROWS rows x 32 columns) tiles with K chunks of kc channels
+static int plain_params(const sg3_conv2d_params& q, int BM, int ROWS, int kc, PlainConvParams& p) {
+    p.x = q.x; p.wp = q.wPacked; p.inScale = q.inScale; p.inShift = q.inShift; p.bias = q.bias; p.slope = q.slope; p.out = q.out;
+    p.wScale = q.wScale;
+    p.N = q.N; p.I = q.I; p.O = q.O; p.H = q.H; p.W = q.W; p.stride = q.stride; p.pad = q.pad; p.act = q.act;
+    p.outH = (q.H + 2 * q.pad - q.k) / q.stride + 1; p.outW = (q.W + 2 * q.pad - q.k) / q.stride + 1;
+    p.nch = ceil_div(q.I, kc);
+    p.xTiles = ceil_div(p.outW, 32); p.yTiles = ceil_div(p.outH, ROWS); p.mTiles = ceil_div(q.O, BM);
+    const long long total = (long long)p.xTiles * p.yTiles * p.mTiles * q.N;
+    if (total > 0x7fffffffLL) { set_error("conv2d: grid too large"); return SG3_BAD_ARG; }
+    p.totalBlocks = (int)total;
+    return SG3_OK;
 }
 
 template <int KS, int STRIDE, int WM, int WN, int TM, int TN>
@@ -485,19 +476,12 @@ static int launch_plain_f16x3(const sg3_conv2d_params& q, hipStream_t st) {
     constexpr int BM = WM * TM * 32, ROWS = WN * TN;
     constexpr size_t ldsBytes = ((size_t)BM * (KS * KS * 32 + 8) + 4 * (size_t)((ROWS - 1) * STRIDE + KS) * (31 * STRIDE + KS) * 8) * sizeof(_Float16);
     PlainConvParams p;
-    p.x = q.x; p.wp = q.wPacked; p.inScale = q.inScale; p.inShift = q.inShift; p.bias = q.bias; p.slope = q.slope; p.out = q.out;
-    p.wScale = q.wScale;
-    p.N = q.N; p.I = q.I; p.O = q.O; p.H = q.H; p.W = q.W; p.stride = STRIDE; p.pad = q.pad; p.act = q.act;
-    p.outH = (q.H + 2 * q.pad - KS) / STRIDE + 1; p.outW = (q.W + 2 * q.pad - KS) / STRIDE + 1;
-    p.nch = ceil_div(q.I, 16);
-    p.xTiles = ceil_div(p.outW, 32); p.yTiles = ceil_div(p.outH, ROWS); p.mTiles = ceil_div(q.O, BM);
-    const long long total = (long long)p.xTiles * p.yTiles * p.mTiles * q.N;
-    if (total > 0x7fffffffLL) { set_error("conv2d: grid too large"); return SG3_BAD_ARG; }
-    p.totalBlocks = (int)total;
+    const int rc = plain_params(q, BM, ROWS, 16, p);
+    if (rc != SG3_OK) return rc;
     auto kern = conv2d_f16x3_kernel<KS, STRIDE, WM, WN, TM, TN>;
     if (ldsBytes > 64 * 1024)
         SG3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes));
-    hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(256), ldsBytes, st, p, q.rangeFlag);
+    hipLaunchKernelGGL(kern, dim3((unsigned)p.totalBlocks), dim3(256), ldsBytes, st, p, q.rangeFlag);
     SG3_LAUNCH_CHECK("conv2d_f16x3_kernel");
     return SG3_OK;
 }
@@ -529,18 +513,10 @@ static int dispatch_plain_f16x3(const sg3_conv2d_params& q, hipStream_t st) {
 
 template <int KS, int STRIDE, int WM, int WN, int TM, int TN>
 static int launch_plain(const sg3_conv2d_params& q, hipStream_t st) {
-    constexpr int BM = WM * TM * 32, ROWS = WN * TN, KC = (KS == 3) ? 8 : 16;
     PlainConvParams p;
-    p.x = q.x; p.wp = q.wPacked; p.inScale = q.inScale; p.inShift = q.inShift; p.bias = q.bias; p.slope = q.slope; p.out = q.out;
-    p.wScale = q.wScale;
-    p.N = q.N; p.I = q.I; p.O = q.O; p.H = q.H; p.W = q.W; p.stride = q.stride; p.pad = q.pad; p.act = q.act;
-    p.outH = (q.H + 2 * q.pad - KS) / STRIDE + 1; p.outW = (q.W + 2 * q.pad - KS) / STRIDE + 1;
-    p.nch = ceil_div(q.I, KC);
-    p.xTiles = ceil_div(p.outW, 32); p.yTiles = ceil_div(p.outH, ROWS); p.mTiles = ceil_div(q.O, BM);
-    const long long total = (long long)p.xTiles * p.yTiles * p.mTiles * q.N;
-    if (total > 0x7fffffffLL) { set_error("conv2d: grid too large"); return SG3_BAD_ARG; }
-    p.totalBlocks = (int)total;
-    hipLaunchKernelGGL((conv2d_mfma_kernel<KS, STRIDE, WM, WN, TM, TN>), dim3((unsigned)total), dim3(256), 0, st, p);
+    const int rc = plain_params(q, WM * TM * 32, WN * TN, ConvK<KS>::KC, p);
+    if (rc != SG3_OK) return rc;
+    hipLaunchKernelGGL((conv2d_mfma_kernel<KS, STRIDE, WM, WN, TM, TN>), dim3((unsigned)p.totalBlocks), dim3(256), 0, st, p);
     SG3_LAUNCH_CHECK("conv2d_mfma_kernel");
     return SG3_OK;
 }
@@ -577,7 +553,7 @@ int sg3_conv2d_pack(const float* w, const float* outScale, float* wPacked, float
         SG3_LAUNCH_CHECK("conv2d_pack_f16x3_kernel");
         return SG3_OK;
     }
-    const int kc = k == 3 ? 8 : 16;
+    const int kc = k == 3 ? ConvK<3>::KC : ConvK<1>::KC;
     hipLaunchKernelGGL(conv2d_pack_kernel, dim3(O), dim3(256), 0, (hipStream_t)stream, w, outScale, wPacked, O, I, k * k, kc, ceil_div(I, kc));
     SG3_LAUNCH_CHECK("conv2d_pack_kernel");
     return SG3_OK;

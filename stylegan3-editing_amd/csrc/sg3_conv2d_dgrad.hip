@@ -16,12 +16,9 @@
 // Epilogue, per written element:  v = acc (+ addend, through element strides);  v *= (act > 0 ? 1 : slope[i])  when `act` is given
 // (the derivative of the PReLU whose saved output, or pre-activation, is `act`).  The input size H x W is a parameter: a stride-2
 // output size does not determine it.  Every element of dx is written exactly once.
-#include "sg3_common.h"
+#include "sg3_igemm_f32.h"
 
 namespace sg3 {
-
-typedef float dg_f32x16 __attribute__((ext_vector_type(16)));
-typedef float dg_f32x4 __attribute__((ext_vector_type(4)));
 
 struct DgradParams {
     const float* dy; const float* wp; float* dx; const float* act; const float* slope; const float* addend;
@@ -33,7 +30,7 @@ struct DgradParams {
 template <int KS, int STRIDE, int WM, int WN, int TM, int TN>
 __global__ void __launch_bounds__(256)
 conv2d_dgrad_kernel(DgradParams p) {
-    constexpr int TAPS = KS * KS, KC = (KS == 3) ? 8 : 16;
+    constexpr int TAPS = ConvK<KS>::TAPS, KC = ConvK<KS>::KC;
     constexpr int BM = WM * TM * 32;
     constexpr int ROWS = WN * TN;
     constexpr int PH = ROWS + 2, PW = 34;              // class rows / columns of the tile plus the margin of one
@@ -67,7 +64,7 @@ conv2d_dgrad_kernel(DgradParams p) {
     // Four accumulators per tile, one per k lane pair of the fragment (summed in the epilogue): a single accumulator would be a chain
     // of taps x O / 2 dependent additions, whose rounding error grows with its length and is several times that of a library GEMM
     // over O; four chains of a quarter the length also leave the matrix pipe no dependent back-to-back issue.
-    dg_f32x16 acc[4][TM][TN];
+    f32x16 acc[4][TM][TN];
 #pragma unroll
     for (int q = 0; q < 4; q++)
 #pragma unroll
@@ -83,18 +80,18 @@ conv2d_dgrad_kernel(DgradParams p) {
     for (int tap = 0; tap < TAPS; tap++)
         any = any || ((((py + p.pad - tap / KS) | (px + p.pad - tap % KS)) & (STRIDE - 1)) == 0);
 
-    dg_f32x4 ra[A_PER];
+    f32x4 ra[A_PER];
     float rb[B_PER];
 
     auto fetch = [&](int ch) {
 #pragma unroll
         for (int q = 0; q < A_PER; q++) {
             const int v = tid + 256 * q;
-            dg_f32x4 val = {0.f, 0.f, 0.f, 0.f};
+            f32x4 val = {0.f, 0.f, 0.f, 0.f};
             if (A_V4 % 256 == 0 || v < A_V4) {
                 const int row = v / (TAPS * KC / 4), col = v % (TAPS * KC / 4);
                 if (i0 + row < p.I)
-                    val = *reinterpret_cast<const dg_f32x4*>(p.wp + ((size_t)(i0 + row) * p.nch + ch) * (TAPS * KC) + col * 4);
+                    val = *reinterpret_cast<const f32x4*>(p.wp + ((size_t)(i0 + row) * p.nch + ch) * (TAPS * KC) + col * 4);
             }
             ra[q] = val;
         }
@@ -117,7 +114,7 @@ conv2d_dgrad_kernel(DgradParams p) {
             const int v = tid + 256 * q;
             if (A_V4 % 256 == 0 || v < A_V4) {
                 const int row = v / (TAPS * KC / 4), col = v % (TAPS * KC / 4);
-                *reinterpret_cast<dg_f32x4*>(sA + row * AS + col * 4) = ra[q];
+                *reinterpret_cast<f32x4*>(sA + row * AS + col * 4) = ra[q];
             }
         }
 #pragma unroll
@@ -144,13 +141,13 @@ conv2d_dgrad_kernel(DgradParams p) {
                 const int oy = (ty >> SH) + 1, ox = (tx >> SH) + 1;                      // 0 .. 2 inside the patch margin
 #pragma unroll
                 for (int c8 = 0; c8 < KC / 8; c8++) {
-                    dg_f32x4 fa[TM], fb[TN];
+                    f32x4 fa[TM], fb[TN];
 #pragma unroll
                     for (int a = 0; a < TM; a++)
-                        fa[a] = *reinterpret_cast<const dg_f32x4*>(sA + ((wm * TM + a) * 32 + li) * AS + tap * KC + c8 * 8 + 4 * lh);
+                        fa[a] = *reinterpret_cast<const f32x4*>(sA + ((wm * TM + a) * 32 + li) * AS + tap * KC + c8 * 8 + 4 * lh);
 #pragma unroll
                     for (int b = 0; b < TN; b++)
-                        fb[b] = *reinterpret_cast<const dg_f32x4*>(sB + (2 * c8 + lh) * PLANE + ((wn * TN + b + oy) * PW + li + ox) * 4);
+                        fb[b] = *reinterpret_cast<const f32x4*>(sB + (2 * c8 + lh) * PLANE + ((wn * TN + b + oy) * PW + li + ox) * 4);
 #pragma unroll
                     for (int q = 0; q < 4; q++)
 #pragma unroll
@@ -187,7 +184,7 @@ conv2d_dgrad_kernel(DgradParams p) {
 
 template <int KS, int STRIDE, int WM, int WN, int TM, int TN>
 static int launch_dgrad(const sg3_conv2d_dgrad_params& q, hipStream_t st) {
-    constexpr int BM = WM * TM * 32, ROWS = WN * TN, KC = (KS == 3) ? 8 : 16;
+    constexpr int BM = WM * TM * 32, ROWS = WN * TN, KC = ConvK<KS>::KC;
     DgradParams p;
     p.dy = q.dy; p.wp = q.wPacked; p.dx = q.dx; p.act = q.act; p.slope = q.slope; p.addend = q.addend;
     for (int d = 0; d < 4; d++) p.addStride[d] = q.addStride[d];

@@ -23,7 +23,7 @@
 // renumbered so that the M tiles sharing an input patch, and neighbouring patches, sit on one XCD.
 //
 // demodulation (dcoef) is applied in the epilogue; bias/activation belong to the following filtered_lrelu.
-#include "sg3_common.h"
+#include "sg3_igemm_f32.h"
 #include "sg3_split.h"
 #include "sg3_modconv_f23.h"
 #include <algorithm>
@@ -31,10 +31,8 @@
 
 namespace sg3 {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// ConvK, packed_kc, f16x3_chunks and FLAT_NPIX: sg3_modconv_plan.h (packing and tile constants the plan shares with the kernels)
+// packed_kc, f16x3_chunks and FLAT_NPIX: sg3_modconv_plan.h (packing and tile constants the plan shares with the kernels);
+// ConvK, xcd_block and mfma_c_row: sg3_igemm_f32.h
 
 struct ConvParams {
     const void* x; const float* wp; const float* sIn; const float* dcoef; void* out;
@@ -73,11 +71,7 @@ modconv_mfma_kernel(ConvParams p) {
     const int li = lane & 31, lh = lane >> 5;
 
     // block -> (m tile, x tile, y tile, sample); consecutive logical ids share an XCD
-    int bid = blockIdx.x;
-    {
-        const int nb = p.totalBlocks, q = nb >> 3, r = nb & 7, xcd = bid & 7, k = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-    }
+    int bid = xcd_block(blockIdx.x, p.totalBlocks);
     const int mt = bid % p.mTiles; bid /= p.mTiles;
     const int xt = bid % p.xTiles; bid /= p.xTiles;
     const int yt = bid % p.yTiles; const int n = bid / p.yTiles;
@@ -235,11 +229,7 @@ modconv_f16x3_kernel(ConvParams p) {
     const int wm = wave / WN, wn = wave % WN;
     const int li = lane & 31, lh = lane >> 5;
 
-    int bid = blockIdx.x;
-    {
-        const int nb = p.totalBlocks, q = nb >> 3, r = nb & 7, xcd = bid & 7, k = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-    }
+    int bid = xcd_block(blockIdx.x, p.totalBlocks);
     const int mt = bid % p.mTiles; bid /= p.mTiles;
     const int xt = bid % p.xTiles; bid /= p.xTiles;
     const int yt = bid % p.yTiles; const int n = bid / p.yTiles;
@@ -469,7 +459,7 @@ modconv_f16x3_kernel(ConvParams p) {
             const unsigned rowOff = laneBase + (unsigned)(gy * p.outPitch) * (unsigned)sizeof(T);
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                const unsigned off = rowOff + (unsigned)((r & 3) + 8 * (r >> 2)) * planeB;
+                const unsigned off = rowOff + (unsigned)mfma_c_row(r) * planeB;
                 const float v = acc[0][b][r] * d[r];
                 if (sizeof(T) == 4) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), orr, (int)off, 0, 0);
                 else __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, (_Float16)v), orr, (int)off, 0, 0);
@@ -524,11 +514,7 @@ modconv_flat_kernel(ConvParams p) {
     const int wm = wave / WN, wn = wave % WN;
     const int li = lane & 31, lh = lane >> 5;
 
-    int bid = blockIdx.x;
-    {
-        const int nb = p.totalBlocks, q = nb >> 3, r = nb & 7, xcd = bid & 7, k = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-    }
+    int bid = xcd_block(blockIdx.x, p.totalBlocks);
     // Small grids (batch 1 on the 36^2 maps: 96 tiles for 256 CUs, each walking all 32 K chunks with nobody to hide its latency):
     // the K chunks of a tile are split over kSplits workgroups, innermost in the block order so that they run side by side; each
     // writes its raw sums to partial[ks] and modconv_split_reduce_kernel adds them in order and applies the demodulation.
@@ -632,7 +618,7 @@ modconv_flat_kernel(ConvParams p) {
         const __amdgpu_buffer_rsrc_t dr = __builtin_amdgcn_make_buffer_rsrc((void*)(p.dcoef + (size_t)n * p.O), (short)0, p.O * 4, 0x00020000);
 #pragma unroll
         for (int r = 0; r < 16; r++)
-            d[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(dr, (oL + (r & 3) + 8 * (r >> 2)) * 4, 0, 0));
+            d[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(dr, (oL + mfma_c_row(r)) * 4, 0, 0));
     }
     const _Float16* aBase = sA + (wm * 32 + li) * AS + lh * 8;
     const _Float16* bBase = sB + (lh * NPART) * BPLANE;
@@ -677,7 +663,7 @@ modconv_flat_kernel(ConvParams p) {
 #pragma unroll
             for (int r = 0; r < 16; r++) {
                 const float v = acc[b][r];               // a scalar first: hipcc 7.2 compiles __builtin_bit_cast of a vector ELEMENT as a read of element 0
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), prr, (int)(base + (unsigned)((r & 3) + 8 * (r >> 2)) * planeF), 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), prr, (int)(base + (unsigned)mfma_c_row(r) * planeF), 0, 0);
             }
         }
         return;
@@ -692,7 +678,7 @@ modconv_flat_kernel(ConvParams p) {
         const unsigned base = pf[b] >= 0 ? (unsigned)oL * planeB + (unsigned)pf[b] * (unsigned)sizeof(T) : 0x80000000u;
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-            const int orow = (r & 3) + 8 * (r >> 2);
+            const int orow = mfma_c_row(r);
             const float v = acc[b][r] * d[r];
             if (desc) {
                 if (sizeof(T) == 4) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), orr, (int)(base + (unsigned)orow * planeB), 0, 0);
@@ -742,11 +728,7 @@ modconv1_f16x3_kernel(ConvParams p) {
     // staging task of this thread: a PAIR of adjacent pixels x the 8 channels of one (k-step, channel-half); wave-uniform group
     const int ssub = wave >> 2, kh = (wave >> 1) & 1;
 
-    int bid = blockIdx.x;
-    {
-        const int nb = p.totalBlocks, q = nb >> 3, r = nb & 7, xcd = bid & 7, k = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-    }
+    int bid = xcd_block(blockIdx.x, p.totalBlocks);
     // grids smaller than the chip: the K stages of a tile split over kSplits workgroups, each writing its share (demodulation
     // applied: the epilogue is linear) to its own fp32 image partial[ks]; modconv_split_reduce_kernel adds the images in order
     const int ks = bid % p.kSplits; bid /= p.kSplits;
@@ -992,14 +974,14 @@ modconv1_f16x3_kernel(ConvParams p) {
             float d[16];
 #pragma unroll
             for (int r = 0; r < 16; r++)
-                d[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(dr, (oL + (r & 3) + 8 * (r >> 2)) * 4, 0, 0));
+                d[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(dr, (oL + mfma_c_row(r)) * 4, 0, 0));
 #pragma unroll
             for (int b = 0; b < TN; b++) {
                 const int px = p0 + (wn * TN + b) * 32 + li;
                 const unsigned base = px < P ? (unsigned)oL * planeB + (unsigned)px * (unsigned)sizeof(T) : 0x80000000u;
 #pragma unroll
                 for (int r = 0; r < 16; r++) {
-                    const unsigned off = base + (unsigned)((r & 3) + 8 * (r >> 2)) * planeB;
+                    const unsigned off = base + (unsigned)mfma_c_row(r) * planeB;
                     const float v = acc[a][b][r] * d[r];
                     if (sizeof(T) == 4) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), orr, (int)off, 0, 0);
                     else __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, (_Float16)v), orr, (int)off, 0, 0);
@@ -1012,7 +994,7 @@ modconv1_f16x3_kernel(ConvParams p) {
     for (int a = 0; a < TM; a++)
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-            const int o = o0 + (wm * TM + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            const int o = o0 + (wm * TM + a) * 32 + mfma_c_row(r) + 4 * lh;
             if (o >= p.O) continue;
             const float d = p.dcoef[(size_t)n * p.O + o];
 #pragma unroll
@@ -1408,7 +1390,7 @@ int64_t sg3_modconv_split_scratch_floats(const sg3_modconv_params* p) {
     sg3_modconv_params q = *p;
     float anything;
     q.splitScratch = &anything; q.splitScratchFloats = INT64_MAX;
-    const ConvPlan pl = plan_modconv(q, conv_cu_count(), ConvKnobs::env(), f23_forced_rows());
+    const ConvPlan pl = plan_modconv(q, device_cu_count(), ConvKnobs::env(), f23_forced_rows());
     if (pl.family == SG3_MODCONV_NONE || pl.kSplits <= 1) return 0;
     return (int64_t)pl.kSplits * p->N * p->O * (p->H + 2 * p->pad - p->k + 1) * (p->W + 2 * p->pad - p->k + 1);
 }
@@ -1417,7 +1399,7 @@ int sg3_modconv_dispatch(const sg3_modconv_params* p, int cus, sg3_modconv_dispa
     using namespace sg3;
     SG3_REQUIRE(p && out, "modconv_dispatch: null argument");
     { const int rc = validate_call(p); if (rc != SG3_OK) return rc; }
-    *out = plan_modconv(*p, cus > 0 ? cus : conv_cu_count(), ConvKnobs::env(), f23_forced_rows());
+    *out = plan_modconv(*p, cus > 0 ? cus : device_cu_count(), ConvKnobs::env(), f23_forced_rows());
     SG3_REQUIRE(out->family != SG3_MODCONV_NONE, "modulated_conv2d: grid too large");
     return SG3_OK;
 }
@@ -1480,7 +1462,7 @@ int sg3_modulated_conv2d(const sg3_modconv_params* p, void* stream) {
     using namespace sg3;
     SG3_REQUIRE(p && p->x && p->wPacked && p->sIn && p->out, "modulated_conv2d: null tensor");
     { const int rc = validate_call(p); if (rc != SG3_OK) return rc; }
-    const ConvPlan pl = plan_modconv(*p, conv_cu_count(), ConvKnobs::env(), f23_forced_rows());
+    const ConvPlan pl = plan_modconv(*p, device_cu_count(), ConvKnobs::env(), f23_forced_rows());
     hipStream_t st = (hipStream_t)stream;
     if (pl.family == SG3_MODCONV_F23) return launch_f23(*p, pl, st);
     return p->dtype == SG3_F32 ? launch_plan<float>(*p, pl, st) : launch_plan<_Float16>(*p, pl, st);

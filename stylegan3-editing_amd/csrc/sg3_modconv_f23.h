@@ -6,18 +6,6 @@
 
 namespace sg3 {
 
-// CUs of the current device, read once per device; 256 without one
-inline int conv_cu_count() {
-    static int cus[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (cus[dev] == 0) {
-        int n = 0;
-        cus[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-    }
-    return cus[dev];
-}
-
 // one planned launch: the dynamic-LDS limit of the instantiation where the plan passes the default 64 KB, then the kernel
 template <typename K, typename... Args>
 static int launch_kernel(K kern, const char* name, const ConvPlan& pl, hipStream_t st, const Args&... args) {

@@ -641,7 +641,7 @@ int f23_force_rows(int rows) { return g_f23_rows.exchange((rows == 4 || rows == 
 int f23_forced_rows() { return g_f23_rows.load(std::memory_order_relaxed); }
 
 int launch_conv_f23(const sg3_modconv_params& q, hipStream_t st) {
-    return launch_f23(q, plan_modconv(q, conv_cu_count(), ConvKnobs::env(), f23_forced_rows()), st);
+    return launch_f23(q, plan_modconv(q, device_cu_count(), ConvKnobs::env(), f23_forced_rows()), st);
 }
 
 } // namespace sg3

@@ -1,8 +1,9 @@
 // sg3_modconv_plan.h -- which kernel, tile and grid a modulated-convolution call takes: ONE pure host function, plan_modconv,
 // shared by the launch (sg3_modulated_conv2d), the scratch query (sg3_modconv_split_scratch_floats) and the read-only ABI query
-// (sg3_modconv_dispatch, which tests read without a GPU).  Plain host C++: no HIP runtime call, no pointer followed.
+// (sg3_modconv_dispatch, which tests read without a GPU).  plan_modconv makes no HIP runtime call and follows no pointer (the
+// header it takes ConvK from, sg3_igemm_f32.h, also holds device helpers of the kernels).
 #pragma once
-#include "sg3_common.h"
+#include "sg3_igemm_f32.h"
 #include <algorithm>
 #include <cstdlib>
 
@@ -12,11 +13,7 @@
 
 namespace sg3 {
 
-// K chunk of the packed fp32 weights per kernel size (modconv_mfma_kernel)
-template <int KS> struct ConvK;
-template <> struct ConvK<3> { static constexpr int TAPS = 9, KC = 8; };
-template <> struct ConvK<1> { static constexpr int TAPS = 1, KC = 16; };
-
+// K chunk of the packed fp32 weights per kernel size (modconv_mfma_kernel): ConvK, sg3_igemm_f32.h
 static inline int packed_kc(int k) { return k == 3 ? ConvK<3>::KC : ConvK<1>::KC; }
 // 16-channel chunks of the f16x3 packing; 1x1 kernels stage two chunks per step, so their count is padded to even
 static inline int f16x3_chunks(int I, int k) { const int c = (I + 15) / 16; return k == 1 ? (c + 1) / 2 * 2 : c; }

@@ -16,15 +16,17 @@ Per row:
 The sibling check.  A crossed row is run again on the other tensor type, same values, same template coordinates, same SPLIT.  In all
 three families the tensor type T enters the kernel through loads and stores alone: same operand rounding, same accumulation order,
 and the fp16 store is `(_Float16)(acc * d)`, round to nearest even as torch's .to(float16).
-  * FLAT, modconv_flat_kernel (csrc/sg3_modconv.hip): x is read by bufld<T>::ld at :597 (csrc/sg3_split.h:12-49: fp16 is widened to
-    fp32, exactly) and is fp32 from there on -- scaled, then split2 / round2 at :617-620; the MFMA order (:654-664) does not name T;
-    the epilogue forms v = acc * d in fp32 and stores v or (_Float16)v (:696-701).  With a K split the partial images are fp32 for
-    both T (:679-680) and modconv_split_reduce_kernel<T> rounds `(T)(v * d)` (:1240).
+  * FLAT, modconv_flat_kernel (csrc/sg3_modconv.hip): x is read by bufld<T>::ld in its `fetch` lambda (struct bufld in
+    csrc/sg3_split.h: fp16 is widened to fp32, exactly) and is fp32 from there on -- scaled, then split2 / round2 in `stage`; the MFMA
+    order (the tap loop) does not name T; the epilogue forms v = acc * d in fp32 and stores v or (_Float16)v (the `desc` loop at the
+    end).  With a K split the partial images are fp32 for both T (the `p.kSplits > 1` branch) and modconv_split_reduce_kernel<T>
+    rounds `(T)(v * d)`.
     Relation asserted: out_half == out_float.to(float16), BIT FOR BIT (0 of 35.7 million elements differ).
-  * ROWS, modconv_f16x3_kernel: load :307, rounding :332-335, MFMA order :361-372, stores :473-475 (predicated form :491 through
-    io<T>::st, csrc/sg3_common.h:38-48).
-  * GEMM1, modconv1_f16x3_kernel: pixel pairs by bufld<T>::ld2 / unpack2 (:805, :816), rounding :817-828, MFMA order :856-907 (M16 and
-    32-wide forms), stores :968-975, :1003-1005, :1021.  The plan splits K for fp32 tensors only, so the K-split rows of this family
+  * ROWS, modconv_f16x3_kernel: load in `fetch`, rounding in `stage`, MFMA order in `mfma_row`, stores in the descriptor branch of
+    the epilogue (predicated form below it through io<T>::st, csrc/sg3_common.h).
+  * GEMM1, modconv1_f16x3_kernel: pixel pairs by bufld<T>::ld2 in `fetch` and unpack2 in `stage`, rounding in `stage`, MFMA order in
+    `mfma_step` and `stage_m16` (32-wide and M16 forms), stores in the three epilogue branches (M16, descriptor, predicated).  The plan
+    splits K for fp32 tensors only, so the K-split rows of this family
     have no sibling with the same summation order; their unsplit variant rows are the ones compared.
     The source of ROWS and GEMM1 reads like FLAT's, the machine code does not: hipcc (default -ffp-contract) compiles their
     `(_Float16)(acc * d)` to ONE v_fma_mixlo_f16, which rounds the exact product to fp16 once, where the fp32 kernel's v_mul_f32
