@@ -999,7 +999,9 @@ struct Stream {
             float v = st.omax;
 #pragma unroll
             for (int m = 32; m > 0; m >>= 1) v = __builtin_fmaxf(v, __shfl_xor(v, m));
-            if (lane == 0) p.ymax[(long long)plane_id * (p.nChunks * p.nStrips) + chunk * p.nStrips + strip] = v;
+            // the maximum of what was STORED: v is the largest fp32 result, and rounding to T is monotone, so its rounding is the largest
+            // stored value (fp16 tensors: up to 2^-11 above v -- a reader that takes v for a bound on |dx| would be told too little)
+            if (lane == 0) p.ymax[(long long)plane_id * (p.nChunks * p.nStrips) + chunk * p.nStrips + strip] = (float)(T)v;
         }
     }
 };
