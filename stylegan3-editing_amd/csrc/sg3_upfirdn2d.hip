@@ -6,7 +6,9 @@
 // sg3_filtered_lrelu.hip covers every SG3 layer), so it is one polyphase
 // gather kernel: a thread owns one output pixel and visits only the filter taps that
 // land on real (non zero-stuffed) input samples.  Taps are staged in LDS once per
-// workgroup, already flipped and scaled, so the inner loop is LDS-broadcast + FMA.
+// workgroup, already flipped but unscaled, so the inner loop is LDS-broadcast + FMA;
+// the sum is multiplied by the gain once, in the accumulate type, as the reference's
+// kernel does (a double tensor keeps double accuracy for any gain).
 #include "sg3_common.h"
 
 namespace sg3 {
@@ -25,12 +27,13 @@ upfirdn2d_gather_kernel(sg3_upfirdn2d_params p) {
         int ky = i / p.fW, kx = i - ky * p.fW;
         int sy = p.flip ? ky : p.fH - 1 - ky;
         int sx = p.flip ? kx : p.fW - 1 - kx;
-        s_f[i] = p.f[sy * p.fStride[0] + sx * p.fStride[1]] * p.gain;
+        s_f[i] = p.f[sy * p.fStride[0] + sx * p.fStride[1]];
     }
     __syncthreads();
 
     const T* __restrict__ px = (const T*)p.x;
     T* __restrict__ py = (T*)p.y;
+    const S gain = (S)p.gain;
     const int64_t total = (int64_t)p.N * p.C * p.yH * p.yW;
     const int64_t gstride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gstride) {
@@ -55,7 +58,7 @@ upfirdn2d_gather_kernel(sg3_upfirdn2d_params p) {
                 acc += io<T>::ld(row + (int64_t)ix * p.xStride[3]) * (S)frow[kx];
             }
         }
-        io<T>::st(py + (int64_t)n * p.yStride[0] + (int64_t)c * p.yStride[1] + (int64_t)oy * p.yStride[2] + (int64_t)ox * p.yStride[3], acc);
+        io<T>::st(py + (int64_t)n * p.yStride[0] + (int64_t)c * p.yStride[1] + (int64_t)oy * p.yStride[2] + (int64_t)ox * p.yStride[3], acc * gain);
     }
 }
 

@@ -72,6 +72,10 @@ def bias_act(x, b=None, dim=1, act='linear', alpha=None, gain=None, clamp=None, 
     assert impl in ['ref', 'cuda']
     call = _call_record(dim, act, alpha, gain, clamp)
     if impl == 'cuda' and x.device.type == 'cuda' and _init():
+        # layout copies are made out here, where autograd sees them: a copy made inside _Fused.forward is saved as a tensor without
+        # history, and the second-order gradient of a permuted x (or a strided b) would be dropped without a word
+        x = x.contiguous(memory_format=_layout(x))
+        b = None if b is None else b.contiguous()
         return _Fused.apply(x, b, call)
     return _bias_act_ref(x, b, call=call)
 
@@ -91,7 +95,8 @@ def _bias_act_ref(x, b=None, dim=1, act='linear', alpha=None, gain=None, clamp=N
 
 
 def _layout(t):
-    return torch.channels_last if (t.ndim > 2 and t.stride(1) == 1) else torch.contiguous_format
+    # channels_last exists for rank 4 only: a rank-3 view with unit stride along dim 1 (a permute(0, 2, 1)) is made contiguous
+    return torch.channels_last if (t.ndim == 4 and t.stride(1) == 1) else torch.contiguous_format
 
 
 def _kernel(call, grad_order, x, b, xref, yref, dy):

@@ -39,6 +39,13 @@ with tu = taps per phase of the up filter (6), td = taps of the down filter (12 
   Configurations without a fused kernel (ToRGB's 1x1 filters in training, 2-D up filters in a forward) run the generic composition
   of the same steps; the same counts are applied with their tap numbers.
 
+  With `generic=True` the bounds count the composition as it runs (x + b -> upfirdn2d -> filtered_lrelu_act_ -> upfirdn2d, each a
+  kernel of its own; every float64 call, every double backward and every configuration without a fused kernel):
+    bias add 1;  up pass T_u + 2 (T_u taps that can meet a real sample: ceil(n / up) per axis of a separable filter, added; the
+    product of the sides of a 2-D one; + 2: the gain product and the stored result);  activation 1;  down pass T_d + 2 (every tap).
+    The adjoint is the same composition with (up, fu) <-> (down, fd) and no bias.  fp16 tensors store every intermediate: x + b,
+    each pass of each upfirdn2d call (two for a separable filter) and the activation, one 2^-11 each.  `unit`: 2^-53 for float64.
+
   fp16 I/O: the inputs are what the kernel read (already rounded); the stored output adds 2^-11 (|ref| + bound), or 2^-25 on
   fp16's subnormal grid (|ref| below 2^-14).
 
@@ -165,6 +172,24 @@ class Ops:
         tu = [-(-s // self.up) for s in self.fu_shape]
         return (1 if bias else 0) + (tu[0] * tu[1] if len(tu) == 2 else 2 * tu[0])
 
+    # ---- the generic composition (module docstring): (roundings, fp16 stores of intermediates) per stage
+    @staticmethod
+    def _generic_pass(shape, factor):
+        t = [-(-n // factor) for n in shape]
+        return (t[0] * t[1] + 2, 1) if len(t) == 2 else (2 * t[0] + 2, 2)
+
+    def generic_u(self, bias=True):
+        n, k = self._generic_pass(self.fu_shape, self.up)
+        return n + (1 if bias else 0), k + (1 if bias else 0)
+
+    def generic_down(self):
+        n, k = self._generic_pass(self.fd_shape, 1)
+        return n, k - 1                       # the last pass stores the result itself
+
+    def generic_adjoint(self):
+        (nu, ku), (nd, kd) = self._generic_pass(self.fd_shape, self.down), self._generic_pass(self.fu_shape, 1)
+        return nu, ku, nd, kd - 1
+
     def n_down(self):
         td = self.fd_shape
         if len(td) == 1:
@@ -272,10 +297,19 @@ def _f16_store(ref, bound):
     return torch.maximum(F16_REL * (ref.abs() + bound), torch.full_like(ref, F16_SUB))
 
 
-def forward_bounds(x, b, fu, fd, up, down, padding, gain, slope, clamp, flip, y_ref=None, fp16=False, scales=None):
-    """(bound_y, bound_u): element-wise bounds on |y(kernel) - y64| and on the kernel's error of u.  x and b as the kernel read them."""
+def forward_bounds(x, b, fu, fd, up, down, padding, gain, slope, clamp, flip, y_ref=None, fp16=False, scales=None, generic=False, unit=U):
+    """(bound_y, bound_u): element-wise bounds on |y(kernel) - y64| and on the kernel's error of u.  x and b as the kernel read them.
+    `generic`: the counts of the generic composition, `unit`: its tensors' unit roundoff (module docstring)."""
     ops = _ops(x.shape[2:], fu, fd, up, down, padding, flip, x.device)
     su, sy_pre, sy_post = scales or abs_scale_forward(x, b, fu, fd, up, down, padding, gain, slope, clamp, flip)      # `scales`: if the caller has them
+    if generic:
+        (nu, ku), (nd, kd) = ops.generic_u(), ops.generic_down()
+        h = F16_REL if fp16 else 0.0
+        bound_u = (nu * unit + ku * h) * SECOND * su
+        bound_y = ((nu + 1) * unit + (ku + 1) * h) * SECOND * sy_pre + (nd * unit + kd * h) * SECOND * sy_post
+        if fp16:
+            bound_y = bound_y + _f16_store(y_ref, bound_y)
+        return bound_y, bound_u
     bound_u = ops.n_u() * U * SECOND * su
     bound_y = ((ops.n_u() + 1) * sy_pre + ops.n_down() * sy_post) * U * SECOND
     if fp16:
@@ -283,7 +317,7 @@ def forward_bounds(x, b, fu, fd, up, down, padding, gain, slope, clamp, flip, y_
     return bound_y, bound_u
 
 
-def ambiguous(u64, bound_u, su, gain, slope, clamp):
+def ambiguous(u64, bound_u, su, gain, slope, clamp, unit=U):
     """(at zero, at the clamp): samples whose decision the kernel's rounding of u may change."""
     g, s = f32(gain), f32(slope)
     at0 = (u64.abs() <= bound_u) & (su > 0)
@@ -292,14 +326,16 @@ def ambiguous(u64, bound_u, su, gain, slope, clamp):
     v = u64 * g
     neg = v < 0
     k = torch.where(neg, s, 1.0).to(torch.float64)
-    err = (bound_u * g + 2 * U * v.abs()) * k * SECOND
+    err = (bound_u * g + 2 * unit * v.abs()) * k * SECOND
     atc = ((v * k).abs() - f32(clamp)).abs() <= err
     return at0, atc
 
 
-def adjoint_bounds(dy, u64, bound_u, su, x_hw, fu, fd, up, down, padding, gain, slope, clamp, flip, dx_ref=None, fp16=False):
+def adjoint_bounds(dy, u64, bound_u, su, x_hw, fu, fd, up, down, padding, gain, slope, clamp, flip, dx_ref=None, fp16=False, generic=False,
+                   unit=U):
     """(bound_dx, widening, n_adj): the element-wise bound on |dx(kernel) - dx64| (widening included), the widening alone, and the
-    rounding count.  `bound_u`, `su`: of the forward that wrote the signs (`forward_bounds`, `abs_scale_forward`)."""
+    rounding count.  `bound_u`, `su`: of the forward that wrote the signs (`forward_bounds`, `abs_scale_forward`).  `generic`, `unit`:
+    as in `forward_bounds` (n_adj then counts an fp16 store as 2^-11 / unit roundings)."""
     n, c = dy.shape[:2]
     ops = _ops(x_hw, fu, fd, up, down, padding, flip, dy.device)
     # the adjoint call runs with (up, fu) <-> (down, fd): its "up" filter is fd, its "down" filter fu
@@ -309,16 +345,21 @@ def adjoint_bounds(dy, u64, bound_u, su, x_hw, fu, fd, up, down, padding, gain, 
     tf = ops.fu_shape
     n_dn = (tf[0] + (tf[0] // 2 + 1 if tf[0] > 1 else 1) + 1) if len(tf) == 1 else (tf[0] * tf[1] // 2 + 2)
     n_adj = n_up + 1 + n_dn
+    if generic:
+        n_up, k_up, n_dn, k_dn = ops.generic_adjoint()
+        h = F16_REL / unit if fp16 else 0.0
+        n_adj = n_up + 1 + n_dn + (k_up + 1 + k_dn) * h
+        n_up = n_up + k_up * h
     sg, sdx = abs_scale_adjoint(dy, u64, x_hw, fu, fd, up, down, padding, gain, slope, clamp, flip)
-    at0, atc = ambiguous(u64, bound_u, su, gain, slope, clamp)
+    at0, atc = ambiguous(u64, bound_u, su, gain, slope, clamp, unit)
     s = f32(slope)
     neg = u64 < 0
     jump = at0.to(torch.float64) * (1.0 - s) + atc.to(torch.float64) * torch.where(neg, s, 1.0).to(torch.float64)
     # the kernel's own g_up: within n_up u sg of the exact one
-    g_up = Ops.apply(ops.B, _planes(dy), transpose=True).reshape(n, c, *ops.u_hw).abs() + n_up * U * SECOND * sg
+    g_up = Ops.apply(ops.B, _planes(dy), transpose=True).reshape(n, c, *ops.u_hw).abs() + n_up * unit * SECOND * sg
     wid = Ops.apply(ops.A, (jump * _adj_gain(gain, up, down) * g_up).reshape(n * c, *ops.u_hw), absolute=True,
                     transpose=True).reshape(n, c, *x_hw)
-    bound = n_adj * U * SECOND * sdx + wid
+    bound = n_adj * unit * SECOND * sdx + wid
     if fp16:
         bound = bound + _f16_store(dx_ref, bound)
     return bound, wid, n_adj
