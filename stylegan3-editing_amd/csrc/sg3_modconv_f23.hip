@@ -29,6 +29,8 @@
 // splits and writes eight 16-byte vectors; the style scales come through the scalar cache.  One barrier per 16-channel chunk.  Waves 4-7 (the second wave of every SIMD) run the
 // chunk body in the order stage-then-MFMA, waves 0-3 MFMA-then-stage, so that one wave's staging arithmetic sits beside the
 // other's matrix instructions instead of both waves alternating in lockstep.
+// Where the B image holds the output transform's 64 KB exchange area (split precision, TN = 7) the chunk pipeline runs on from tile
+// to tile of a persistent workgroup: only its first tile has a prologue (see "ONE PIPELINE OVER THE WORKGROUP'S TILES" below).
 #include "sg3_common.h"
 #include "sg3_split.h"
 #include "sg3_modconv_f23.h"
@@ -102,6 +104,12 @@ template <int AB, int TN, int Q> __device__ __forceinline__ void f23_mfma_row_f1
 #ifndef F23_PRIO_MODE
 #define F23_PRIO_MODE 2
 #endif
+// experiment switch: 1 gives the tile heights whose B image is at least 32 KB but below the 64 KB exchange area (split TN = 4 / 5,
+// fp16 TN = 7) the cross-tile pipeline with a single-buffered exchange; 0 (shipped) leaves them on the per-tile flow
+// (profiles/r14_f23_cross_tile.txt)
+#ifndef F23_XTILE_SINGLE
+#define F23_XTILE_SINGLE 0
+#endif
 typedef unsigned u32x8 __attribute__((ext_vector_type(8)));
 
 // T = float: split precision (SG3_CONV_F16X3_F23, fp32 tensors); T = _Float16: the fp16 operand form (SG3_CONV_F16_F23, fp16 tensors:
@@ -151,15 +159,23 @@ modconv_f23_kernel(F23Params p) {
     unsigned long long wgStart, wgLoop = 0, wgTiles = 0, wgPro = 0, wgEpi = 0, tTop = 0, tLoopEnd = 0;
     F23_STAMP(wgStart);
 #endif
-    for (int tile = tFirst; tile < tEnd; tile += tStep) {
-#ifdef SG3_F23_STAMPS
-    F23_STAMP(tTop);
-#endif
-    int bid = tile;
-    const int mt = bid % p.mTiles; bid /= p.mTiles;
-    const int xt = bid % p.xTiles; bid /= p.xTiles;
-    const int yt = bid % p.yTiles; const int n = bid / p.yTiles;
-    const int o0 = mt * 64, x0 = xt * 32, y0 = yt * (2 * TN);
+    if (tFirst >= tEnd) return;                                       // workgroup-uniform
+
+    // ONE PIPELINE OVER THE WORKGROUP'S TILES (XT != 0).  The K loop's requests lead their use by up to two chunks, so the tile a
+    // request belongs to (REQUEST side: xd, sd, g0, g1 for the samples, aS for the A fragments) is not the tile being accumulated
+    // (OUTPUT side: o0, x0, y0, n, active, the store descriptors).  Each request stream has a cursor (tile, chunk) that moves to the
+    // workgroup's next tile when its chunk index wraps, and past the last tile carries the out-of-range sentinel (answered with
+    // zeros).  Staging, B-fragment reads and the matrix phase do not depend on the tile: B image and A register set follow `par`,
+    // the parity of a chunk counter that runs across tiles (an odd nch flips it from tile to tile).  The last iteration of a tile
+    // stages chunk 0 of the next tile into the other image and requests its chunk 1, so the next tile starts at iteration 0 with
+    // everything a whole iteration old, as in the middle of a tile; only the workgroup's first tile has a prologue.  The output
+    // transform exchanges through the image the tile's last chunk multiplied from, which is free after the loop's closing barrier;
+    // the staged chunk sits in the other image, the next samples age in rb / rsc and the A fragments in a[0:47] meanwhile.
+    //   XT = 1: the image holds the double-buffered 64 KB exchange (split precision at TN = 7)
+    //   XT = 2: single-buffered 32 KB exchange, one more barrier per tile row (F23_XTILE_SINGLE builds only: measured, not shipped)
+    //   XT = 0: smaller images: the per-tile flow -- a prologue per tile, requests never cross a tile boundary, the exchange takes
+    //           both images.  Same code: the cursors are re-seated at every tile and leave for the sentinel at its end.
+    constexpr int XT = BUF >= 65536 ? 1 : (F23_XTILE_SINGLE && BUF >= 32768) ? 2 : 0;
 
     // ---- descriptors, as SGPR quads for the hand-issued loads below ----
     const unsigned HWb = (unsigned)(p.H * p.W) * (unsigned)EB;
@@ -172,31 +188,51 @@ modconv_f23_kernel(F23Params p) {
         d.w = 0x00020000u;
         return d;
     };
-    const u32x4 xd = make_desc(static_cast<const T*>(p.x) + (size_t)n * p.I * p.H * p.W, (unsigned)p.I * HWb);
     const u32x4 wd = make_desc(p.wp, (unsigned)p.mTiles * (unsigned)p.nch * (unsigned)CHUNKB);
-    const u32x4 sd = make_desc(p.sIn + (size_t)n * p.I, (unsigned)p.I * 4u);
+    const int nch = p.nch;
 
     // ---- staging task of this thread: (patch row, pair, channel half) ----
     const int sch = wave & 1;                                         // wave-uniform channel half
     const int srow = (wave >> 1) * 4 + (lane >> 4);
     const int spair = lane & 15;
     const bool sOk = srow < PR;
-    unsigned g0, g1;                                                  // byte offsets of columns (2p, 2p+1) and (2p+2, 2p+3) in a channel plane
-    {
-        const int gy = y0 - p.pad + srow, gx = x0 - p.pad + 2 * spair;
-        const bool rowOk = sOk && (unsigned)gy < (unsigned)p.H;
+    const int sL = srow * 256 + spair * 16 + sch * PLANE;             // + (xi * 2 + part) * 2 * PLANE (split) | + xi * 2 * PLANE (fp16)
+    // ---- A: this wave's six fragments of a chunk ----
+    const unsigned aG = (unsigned)((mb * 4 + xi) * NF) * FRAG + (unsigned)lane * 16u;
+    // ---- B fragment reads ----
+    const int bR = (xi * (SPLIT ? 4 : 2) + lh) * PLANE + (rg * TN) * 256 + pq * 16;  // (hi) plane of this lane's channel half; split: lo at + 2 PLANE
+
+    // ---- request side, input samples: cursor (tile, chunk) of the NEXT request and that tile's descriptors and offsets ----
+    u32x4 xd = {0u, 0u, 0u, 0u}, sd = {0u, 0u, 0u, 0u};
+    unsigned g0 = 0x80000000u, g1 = 0x80000000u;                      // byte offsets of columns (2p, 2p+1) and (2p+2, 2p+3) in a channel plane
+    int rbTile = tFirst, rbCh = 0;
+    auto seek_b = [&](int t) __attribute__((always_inline)) {
+        rbTile = t; rbCh = 0;
+        // past the workgroup's last tile every sample request is out of range (the descriptors are then those of the first tile: any
+        // valid ones).  One unconditional assignment per variable: stores under a branch keep g0 / g1 in memory (hipcc sinks them
+        // into a store through a pointer phi, which is scratch).
+        const bool rin = t < tEnd;
+        int bid = (rin ? t : tFirst) / p.mTiles;
+        const int xt = bid % p.xTiles; bid /= p.xTiles;
+        const int yt = bid % p.yTiles; const int rn = bid / p.yTiles;
+        xd = make_desc(static_cast<const T*>(p.x) + (size_t)rn * p.I * p.H * p.W, (unsigned)p.I * HWb);
+        sd = make_desc(p.sIn + (size_t)rn * p.I, (unsigned)p.I * 4u);
+        const int gy = yt * (2 * TN) - p.pad + srow, gx = xt * 32 - p.pad + 2 * spair;
+        const bool rowOk = rin && sOk && (unsigned)gy < (unsigned)p.H;
         g0 = rowOk && (unsigned)gx < (unsigned)p.W ? (unsigned)(gy * p.W + gx) * (unsigned)EB : 0x80000000u;
         // a thread requests its own column pair and the pair to its right (the neighbour's own pair: an L1 hit of the same
         // instruction's lines): the same 16 requests per chunk as a form that passes the neighbour's pair through DPP and lets only
         // the last lane of a row fetch its halo pair, but without the 16 v_mov_b32_dpp per thread and chunk
         g1 = rowOk && (unsigned)(gx + 2) < (unsigned)p.W ? (unsigned)(gy * p.W + gx + 2) * (unsigned)EB : 0x80000000u;
-    }
-    const int sL = srow * 256 + spair * 16 + sch * PLANE;             // + (xi * 2 + part) * 2 * PLANE (split) | + xi * 2 * PLANE (fp16)
-    // ---- A: this wave's six fragments of a chunk ----
-    const unsigned aG = (unsigned)((mb * 4 + xi) * NF) * FRAG + (unsigned)lane * 16u;
-    const unsigned aS = (unsigned)mt * (unsigned)p.nch * (unsigned)CHUNKB;             // + chunk * CHUNKB + fragment * FRAG (scalar offset)
-    // ---- B fragment reads ----
-    const int bR = (xi * (SPLIT ? 4 : 2) + lh) * PLANE + (rg * TN) * 256 + pq * 16;  // (hi) plane of this lane's channel half; split: lo at + 2 PLANE
+    };
+    // ---- request side, A fragments: the late waves' cursor runs one chunk behind the early waves' (chunk body below) ----
+    unsigned aS = 0;                                                  // + chunk * CHUNKB + fragment * FRAG (scalar offset)
+    int raTile = tFirst, raCh = 0, raPar = 0;                         // raPar: register set of the next request (running chunk parity)
+    bool raIn = false;
+    auto seek_a = [&](int t) __attribute__((always_inline)) {
+        raTile = t; raCh = 0; raIn = t < tEnd;
+        aS = raIn ? (unsigned)(t % p.mTiles) * (unsigned)nch * (unsigned)CHUNKB : 0u;
+    };
 
     // the kernel's accumulator-register allocation covers what the asm statements name (the highest register named as a clobber sizes
     // it); the compiler itself stays within its arch VGPRs (AUDIT: no v_accvgpr_* outside the asm statements)
@@ -204,7 +240,6 @@ modconv_f23_kernel(F23Params p) {
     else if constexpr (TN == 5) asm volatile("" ::: "a127");
     else asm volatile("" ::: "a111");
     static_assert(TN == 4 || TN == 5 || TN == 7, "accumulator-register reservation is written for these tile heights");
-    F23Seq<48, 16 * TN>::zero();
 
     // All vector-memory loads of the K loop are issued and waited for BY HAND (inline asm): the two request streams -- A fragments,
     // input samples -- are consumed in a different order than they are issued, and hipcc, merging the loop's paths, drains the whole
@@ -232,13 +267,14 @@ modconv_f23_kernel(F23Params p) {
     // of the statement, and an SGPR written by a VALU instruction needs 5 wait states before a vector-memory instruction reads it
     // (descriptor or scalar offset) -- the compiler pads that hazard for its own instructions, not for ones inside an asm string.
     // (Seen with the persistent tile loop, which pushed the kernel into SGPR spills: stale descriptors, wrong samples staged.)
-    auto fetch_a = [&](int ch) {
-        const unsigned so = aS + (unsigned)ch * CHUNKB;               // wave-uniform
-        const unsigned vo = ch < p.nch ? aG : 0x80000000u;            // beyond the last chunk: out of range, answered with zeros
-        // chunk parity picks the register set: the set of chunk ch was last read by the MFMAs of chunk ch - 2, issued long before
+    auto fetch_a = [&]() __attribute__((always_inline)) {
+        const unsigned so = aS + (unsigned)raCh * CHUNKB;             // wave-uniform
+        const unsigned vo = raIn ? aG : 0x80000000u;                  // beyond the last tile's last chunk: out of range, answered with zeros
+        const int set = raPar;
+        // running chunk parity picks the register set: it was last read by the MFMAs of the chunk two back, issued long before
         if constexpr (!SPLIT) {
             // fp16 form: three fragments (one per filter row) in a[0:11] | a[24:35]
-            if (ch & 1)
+            if (set)
                 asm volatile("s_nop 4\n\t"
                              "buffer_load_dwordx4 a[24:27], %0, %1, %2 offen\n\t"
                              "buffer_load_dwordx4 a[28:31], %0, %1, %2 offen offset:1024\n\t"
@@ -253,7 +289,7 @@ modconv_f23_kernel(F23Params p) {
                              :: "v"(vo), "s"(wd), "s"(so)
                              : "memory", "a0", "a1", "a2", "a3", "a4", "a5", "a6", "a7", "a8", "a9", "a10", "a11");
         } else
-        if (ch & 1)
+        if (set)
             asm volatile("s_nop 4\n\t"
                          "buffer_load_dwordx4 a[24:27], %0, %1, %2 offen\n\t"
                          "buffer_load_dwordx4 a[28:31], %0, %1, %2 offen offset:1024\n\t"
@@ -275,12 +311,14 @@ modconv_f23_kernel(F23Params p) {
                          :: "v"(vo), "s"(wd), "s"(so), "s"(so + 3 * FRAG)
                          : "memory", "a0", "a1", "a2", "a3", "a4", "a5", "a6", "a7", "a8", "a9", "a10", "a11", "a12", "a13", "a14", "a15",
                            "a16", "a17", "a18", "a19", "a20", "a21", "a22", "a23");
+        raPar ^= 1;
+        if (++raCh == nch) seek_a(XT ? raTile + tStep : tEnd);        // per-tile flow: the cursor leaves at the tile's end
     };
     // wait until all but the N youngest loads have landed: the fragments requested one iteration ago are in their register set (no
     // landing copies: even and odd chunks own a set each and the MFMA statements name the set of their chunk)
 #define F23_LAND(N) asm volatile("s_waitcnt vmcnt(" F23_CNT(N) ")" ::: "memory")
-    auto fetch_b = [&](int ch) {
-        const bool in = ch < p.nch;
+    auto fetch_b = [&]() __attribute__((always_inline)) {
+        const int ch = rbCh;
         unsigned cf[8];
 #pragma unroll
         for (int c = 0; c < 8; c++) {
@@ -290,8 +328,9 @@ modconv_f23_kernel(F23Params p) {
         // the eight style scales of (chunk, channel half) arrive through the SCALAR cache, straight into scalar registers (a vector load
         // + v_readlane per channel costs 15-29 cycles per readlane beside the partner wave's matrix instructions, profiles/r04_mfma_valu_coissue.txt);
         // the descriptor covers this sample's I scales and the range check is per dword: channels beyond I (they alias channel 0 of the
-        // input) and chunks beyond the last read zeros
-        const unsigned v0 = in ? g0 : 0x80000000u, v1 = in ? g1 : 0x80000000u;
+        // input) read zeros.  Past the last tile the sample offsets g0 / g1 are the out-of-range sentinel; the scales then read are
+        // never used
+        const unsigned v0 = g0, v1 = g1;
         const unsigned ss = (unsigned)(ch * 16 + sch * 8) * 4u;        // wave-uniform
         // split: a column pair is 8 bytes (dwordx2); fp16: 4 bytes (dword) -- same sixteen requests, same wait counts
 #define F23_REQ_B(LD) \
@@ -320,6 +359,7 @@ modconv_f23_kernel(F23Params p) {
                      : "v"(v0), "v"(v1), "s"(xd), "s"(cf[4]), "s"(cf[5]), "s"(cf[6]), "s"(cf[7]) : "memory")
         if constexpr (SPLIT) { F23_REQ_B("buffer_load_dwordx2"); } else { F23_REQ_B("buffer_load_dword"); }
 #undef F23_REQ_B
+        if (++rbCh == nch) seek_b(XT ? rbTile + tStep : tEnd);          // per-tile flow: the cursor leaves at the tile's end
     };
     // AUDIT after every edit (tools/audit_f23_asm.py on the -save-temps .s): between a hand-issued load and the wait that covers it
     // hipcc must not read or copy the destination registers (it treats them as written when the load is issued).
@@ -328,8 +368,20 @@ modconv_f23_kernel(F23Params p) {
 #define F23_WAIT_B(N) asm volatile("s_waitcnt vmcnt(" F23_CNT(N) ") lgkmcnt(0)" : "+s"(rsc), "+v"(rb[0][0]), "+v"(rb[0][1]), "+v"(rb[1][0]), "+v"(rb[1][1]), "+v"(rb[2][0]), "+v"(rb[2][1]), \
         "+v"(rb[3][0]), "+v"(rb[3][1]), "+v"(rb[4][0]), "+v"(rb[4][1]), "+v"(rb[5][0]), "+v"(rb[5][1]), "+v"(rb[6][0]), "+v"(rb[6][1]), "+v"(rb[7][0]), "+v"(rb[7][1]) :: "memory")
     static_assert(NB == F23_NB && NA == (SPLIT ? 6 : 3), "the wait counts below are written for these request sizes");
-    // "all but the A request's loads": six (split) | three (fp16) younger loads stay out
-#define F23_WAIT_B_NA() do { if constexpr (SPLIT) { F23_WAIT_B(6); } else { F23_WAIT_B(3); } } while (0)
+    // The staging block waits for "all but the A request's loads": six (split) | three (fp16) younger loads stay out.  The first iteration of a tile that had no prologue finds the 4 TN stores of the previous tile's output transform behind the two
+    // requests in the queue (stores count in vmcnt like loads, in order): the same two waits with those stores left out as well, so
+    // that the late waves, whose staging block opens the iteration, do not sit out the last rows' write acknowledgements.
+    // (The unadjusted counts would be correct too, only slower: they wait for more, never for less.)
+    // The counted wait is OPERAND-LESS and the staging block keeps ONE statement that names rb / rsc (F23_HOLD_B): two alternative
+    // statements with read-write operands make the registers a phi of two branches, and hipcc then copies all 32 of them in FRONT
+    // of one of the waits -- stale samples whenever a load is late (seen as a rare bit difference between two runs; the audit
+    // models the queue since).  The trailing comment tells the audit how many of the waited-out entries are stores.
+    constexpr int NST = 4 * TN;
+    static_assert(F23_NB + NST <= 63, "vmcnt is a six-bit count");
+#define F23_WAIT_ST(N) asm volatile("s_waitcnt vmcnt(%c0) ; +%c1 stores" :: "n"((N) + NST), "n"(NST) : "memory")
+#define F23_WAIT_N(N) asm volatile("s_waitcnt vmcnt(%c0)" :: "n"(N) : "memory")
+#define F23_HOLD_B() asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(rsc), "+v"(rb[0][0]), "+v"(rb[0][1]), "+v"(rb[1][0]), "+v"(rb[1][1]), "+v"(rb[2][0]), "+v"(rb[2][1]), \
+        "+v"(rb[3][0]), "+v"(rb[3][1]), "+v"(rb[4][0]), "+v"(rb[4][1]), "+v"(rb[5][0]), "+v"(rb[5][1]), "+v"(rb[6][0]), "+v"(rb[6][1]), "+v"(rb[7][0]), "+v"(rb[7][1]) :: "memory")
 
     auto stage = [&](int buf) {
         unsigned char* dst = sm + buf * BUF + sL;
@@ -410,7 +462,7 @@ modconv_f23_kernel(F23Params p) {
         if constexpr (SPLIT) f.l = *reinterpret_cast<const v8h*>(src + 2 * PLANE);
     };
     // an M block of pure channel padding (O = 203: channels 224..255 of the fourth tile) stages and synchronises but issues no MFMAs
-    const bool active = o0 + mb * 32 < p.O;                                  // wave-uniform
+    bool active = false;                                                     // wave-uniform, OUTPUT side: set per tile below
     auto mfma_chunk = [&](auto aset, int buf) {
         constexpr int AB = decltype(aset)::value;                                // 0 | 24: register set of this chunk's A fragments
         if (!active) return;
@@ -445,17 +497,18 @@ modconv_f23_kernel(F23Params p) {
 #endif
     };
 
-    // Chunk body: MFMA loop on chunk ch (B image and A register set ch & 1) and the staging block
+    // Chunk body: MFMA loop on chunk ch (B image and A register set `par`) and the staging block; k, j count chunks along the
+    // workgroup's whole walk (per-tile flow: along the tile)
     //   H(k, j) = wait B(k) | stage(k) into the other image | request B(k+1) | wait A(j) | request A(j+1)
     //   waves 0-3 ("early"):  MFMA(ch) | H(ch+1, ch+1) | barrier        -- lands what the NEXT iteration multiplies with
     //   waves 4-7 ("late"):   H(ch+1, ch) | MFMA(ch) | barrier          -- lands what THIS iteration multiplies with
     // so on every SIMD one wave's staging arithmetic runs beside the other's matrix instructions, and every request (A: 6 loads,
     // B: 17) is a whole iteration old when it is waited for.  Load queue, oldest first, when an iteration starts:
     // early B(ch+1), A(ch+1);  late B(ch+1), A(ch).  Inside H: wait B with 6 younger loads (the A request), land A with 17 (the B
-    // request just issued).  Only the late waves' very first wait finds a different queue (the common prologue leaves B(1) alone
-    // behind it): an extra operand-less s_waitcnt makes it exact.
+    // request just issued).  Only the late waves' first wait after a prologue finds a different queue (the common prologue leaves
+    // B(1) alone behind it): an extra operand-less s_waitcnt makes it exact.  At a tile boundary without a prologue the queue is the
+    // steady-state one with the output transform's stores behind it (F23_WAIT_ST).
     const bool late = wave >= 4;                                             // wave-uniform: second wave of its SIMD
-    const int nch = p.nch;
 #if F23_PRIO_MODE == 2
     if (late) __builtin_amdgcn_s_setprio(1);
 #elif F23_PRIO_MODE == 4
@@ -463,13 +516,32 @@ modconv_f23_kernel(F23Params p) {
 #elif F23_PRIO_MODE == 3
     __builtin_amdgcn_s_setprio(1);
 #endif
-    fetch_a(0);
-    fetch_b(0);
-    F23_WAIT_B(0);                                                           // everything, A(0) included
-    stage(0);
-    fetch_b(1);
-    if (!late) { F23_LAND(F23_NB); fetch_a(1); }                                 // the late waves land A(0) in their first H
-    __syncthreads();
+    int par = 0;                                                             // B image and A register set of the chunk being multiplied
+    bool pro = true;                                                         // this tile opens with a prologue (workgroup-uniform)
+    for (int tile = tFirst; tile < tEnd; tile += tStep) {
+#ifdef SG3_F23_STAMPS
+    F23_STAMP(tTop);
+#endif
+    // ---- output side: the tile being accumulated ----
+    int bid = tile;
+    const int mt = bid % p.mTiles; bid /= p.mTiles;
+    const int xt = bid % p.xTiles; bid /= p.xTiles;
+    const int yt = bid % p.yTiles; const int n = bid / p.yTiles;
+    const int o0 = mt * 64, x0 = xt * 32, y0 = yt * (2 * TN);
+    active = o0 + mb * 32 < p.O;
+    F23Seq<48, 16 * TN>::zero();           // after the previous tile's last finish_row, before this tile's first matrix instruction
+    if (pro) {
+        if constexpr (XT == 0) { par = 0; raPar = 0; }
+        seek_a(tile); seek_b(tile);
+        fetch_a();
+        fetch_b();
+        F23_WAIT_B(0);                                                       // everything, A(0) included
+        stage(par);
+        fetch_b();
+        if (!late) { F23_LAND(F23_NB); fetch_a(); }                          // the late waves land A(0) in their first H
+        __syncthreads();
+    }
+    const bool nextTile = XT != 0 && tile + tStep < tEnd;                    // the pipeline runs on into another tile
 #ifdef SG3_F23_STAMPS
     unsigned long long tA = 0, tB = 0, tC = 0, tD = 0, tE = 0, sPre = 0, sMfma = 0, sPost = 0, sBar = 0, tStart, rStart;
     unsigned long long h1 = 0, h2 = 0, h3 = 0, h4 = 0, sH[5] = {0, 0, 0, 0, 0};
@@ -477,39 +549,39 @@ modconv_f23_kernel(F23Params p) {
     rStart = __builtin_amdgcn_s_memrealtime();
 #endif
     for (int ch = 0; ch < nch; ch++) {
-        const int buf = ch & 1;
-        const bool more1 = ch + 1 < nch;
+        const int buf = par;
+        const bool stageNext = ch + 1 < nch || nextTile;                     // the tile's last iteration stages chunk 0 of the next tile
+#ifdef SG3_F23_STAMPS
+        const bool afterStores = false;                                      // the stamps add stores of their own: the plain counts over-wait, safely
+#else
+        const bool afterStores = XT != 0 && !pro && ch == 0;                 // the previous tile's stores sit behind the requests
+#endif
+        auto hblock = [&]() __attribute__((always_inline)) {
+            if (afterStores) F23_WAIT_ST(NA); else F23_WAIT_N(NA);
+            F23_HOLD_B();
+            F23_STAMP(h1);
+            if (stageNext) stage(buf ^ 1);
+            F23_STAMP(h2);
+            fetch_b();
+            F23_STAMP(h3);
+            if (afterStores) F23_WAIT_ST(F23_NB); else F23_LAND(F23_NB);
+            F23_STAMP(h4);
+            fetch_a();
+        };
         F23_STAMP(tA);
         // ONE MFMA site in the loop (the accumulators must not become a phi of two branches: hipcc then keeps two copies of them)
         if (late) {
-            if (ch == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            F23_WAIT_B_NA();
-            F23_STAMP(h1);
-            if (more1) stage(buf ^ 1);
-            F23_STAMP(h2);
-            fetch_b(ch + 2);
-            F23_STAMP(h3);
-            F23_LAND(F23_NB);
-            F23_STAMP(h4);
-            fetch_a(ch + 1);
+            if (ch == 0 && pro) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            hblock();
         }
         F23_STAMP(tB);
         // two copies of the matrix phase, one per register set (the accumulators are asm-named registers, not compiler values: no merge cost)
         if (buf) mfma_chunk(std::integral_constant<int, 24>{}, 1); else mfma_chunk(std::integral_constant<int, 0>{}, 0);
         F23_STAMP(tC);
-        if (!late) {
-            F23_WAIT_B_NA();
-            F23_STAMP(h1);
-            if (more1) stage(buf ^ 1);
-            F23_STAMP(h2);
-            fetch_b(ch + 2);
-            F23_STAMP(h3);
-            F23_LAND(F23_NB);
-            F23_STAMP(h4);
-            fetch_a(ch + 2);
-        }
+        if (!late) hblock();
         F23_STAMP(tD);
         __syncthreads();
+        par ^= 1;
 #ifdef SG3_F23_STAMPS
         F23_STAMP(tE);
         sPre += tB - tA; sMfma += tC - tB; sPost += tD - tC; sBar += tE - tD;
@@ -517,12 +589,19 @@ modconv_f23_kernel(F23Params p) {
           sH[0] += h1 - h0; sH[1] += h2 - h1; sH[2] += h3 - h2; sH[3] += h4 - h3; sH[4] += hE - h4; }
 #endif
     }
-    // The last requests (beyond the last chunk) are never consumed, but the destination registers of the input samples stay RESERVED
-    // until they have landed: the wait names them.  (An operand-less s_waitcnt here let hipcc reuse them for the epilogue's addresses
-    // before the wait, and the returning zeros overwrote those.)  The matrix instructions were issued from asm statements: the
-    // compiler does not know their latency, so the accumulators are given the wait states an XDL result needs before they are read.
-    F23_WAIT_B(0);
-    asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
+    // Per-tile flow: the last requests (beyond the last chunk) are never consumed, but the destination registers of the input samples
+    // stay RESERVED until they have landed: the wait names them.  (An operand-less s_waitcnt here let hipcc reuse them for the
+    // epilogue's addresses before the wait, and the returning zeros overwrote those.)
+    // Cross-tile pipeline: the requests in flight belong to the next tile and are NOT waited for here; the wait that names rb / rsc is
+    // the next staging block's (or the drain behind the tile loop), so the registers stay reserved across the whole output
+    // transform, and nothing in it may wait on the vector-memory counter: the demodulation coefficients come through the scalar cache.
+    if constexpr (XT == 0) F23_WAIT_B(0);
+    // The matrix instructions were issued from asm statements: the compiler does not know their latency, so the accumulators are
+    // given the wait states an XDL result needs before they are read (the s_nop pair; the scalar load rides in front of it).
+    const int ocw = o0 + mb * 32 + 8 * xi;                                    // wave-uniform: first of this wave's eight output channels
+    const u32x4 dd = make_desc(p.dcoef + (size_t)n * p.O, (unsigned)p.O * 4u);
+    u32x8 dsc;                                                                // dcoef[n][ocw .. ocw + 7]; channels beyond O read zero (range check per dword)
+    asm volatile("s_nop 4\n\ts_buffer_load_dwordx8 %0, %1, %2\n\ts_nop 15\n\ts_nop 7\n\ts_waitcnt lgkmcnt(0)" : "=&s"(dsc) : "s"(dd), "s"((unsigned)ocw * 4u) : "memory");
 #ifdef SG3_F23_STAMPS
     if (p.stamps && lane == 0) {
         unsigned long long tEnd; F23_STAMP(tEnd);
@@ -537,14 +616,14 @@ modconv_f23_kernel(F23Params p) {
 
     // ---- output transform: the four xi-waves of an M block exchange their accumulators through LDS, one tile row pair at a time ----
     // wave (xi, mb) finishes accumulator registers 4 xi .. 4 xi + 3 = channels o0 + 32 mb + 8 xi + 4 lh + j of all 32 columns
-    float* X = reinterpret_cast<float*>(sm);                                  // [2][8 waves][16 registers][64 lanes]
-    const int oc = o0 + mb * 32 + 8 * xi + 4 * lh;
+    // exchange area [2][8 waves][16 registers][64 lanes] (XT = 2: [1][8][16][64]).  Cross-tile pipeline: the image the tile's last chunk
+    // multiplied from (par has moved on: the other one holds the next tile's staged chunk 0); per-tile flow: both images
+    float* X = reinterpret_cast<float*>(sm + (XT != 0 ? (par ^ 1) * BUF : 0));
+    static_assert(XT == 0 || BUF >= (XT == 1 ? 65536 : 32768), "the exchange area fits the image");
+    const int oc = ocw + 4 * lh;
     float d[4];
-    {
-        const __amdgpu_buffer_rsrc_t dr = __builtin_amdgcn_make_buffer_rsrc((void*)(p.dcoef + (size_t)n * p.O), (short)0, p.O * 4, 0x00020000);
 #pragma unroll
-        for (int j = 0; j < 4; j++) d[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(dr, (oc + j) * 4, 0, 0));
-    }
+    for (int j = 0; j < 4; j++) d[j] = __builtin_bit_cast(float, lh ? dsc[4 + j] : dsc[j]);
     const unsigned planeB = (unsigned)(p.outH * p.outPitch) * (unsigned)EB;
     const __amdgpu_buffer_rsrc_t orr = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(static_cast<T*>(p.out) + (size_t)n * p.O * p.outH * p.outPitch), (short)0, (int)((unsigned)p.O * planeB), 0x00020000);
@@ -554,7 +633,7 @@ modconv_f23_kernel(F23Params p) {
         constexpr int b = decltype(bc)::value;
         float accv[16];
         F23Seq<48 + 16 * b, 16>::read(accv);
-        float* Xb = X + (b & 1) * (8 * 16 * 64);
+        float* Xb = X + (XT == 2 ? 0 : (b & 1)) * (8 * 16 * 64);
 #pragma unroll
         for (int r = 0; r < 16; r++) Xb[(wave * 16 + r) * 64 + lane] = accv[r];
         __syncthreads();
@@ -574,13 +653,15 @@ modconv_f23_kernel(F23Params p) {
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, h), orr, (int)(rowOff + (unsigned)j * planeB), 0, 0);
             }
         }
+        if constexpr (XT == 2) __syncthreads();             // single-buffered: the next row writes where this one was read
     };
     finish_row(std::integral_constant<int, 0>{}); finish_row(std::integral_constant<int, 1>{});
     finish_row(std::integral_constant<int, 2>{}); finish_row(std::integral_constant<int, 3>{});
     if constexpr (TN > 4) finish_row(std::integral_constant<int, (TN > 4 ? 4 : 0)>{});
     if constexpr (TN > 5) finish_row(std::integral_constant<int, (TN > 5 ? 5 : 0)>{});
     if constexpr (TN > 6) finish_row(std::integral_constant<int, (TN > 6 ? 6 : 0)>{});
-    __syncthreads();                                        // the next tile's first staging block writes where this exchange was read
+    if constexpr (XT != 2) __syncthreads();                 // the next tile's first staging block writes where this exchange was read
+    pro = XT == 0;
 #ifdef SG3_F23_STAMPS
     if (p.stamps && lane == 0) {        // whole-workgroup clock so far, K-loop share of it, tiles walked
         unsigned long long now; F23_STAMP(now);
@@ -593,6 +674,8 @@ modconv_f23_kernel(F23Params p) {
     }
 #endif
     }   // tiles of this workgroup
+    // cross-tile pipeline: the requests past the last tile (sentinel, zeros) are still in flight; this wait names their registers
+    if constexpr (XT != 0) F23_WAIT_B(0);
 }
 
 int64_t f23_packed_floats(int O, int I, bool split) {

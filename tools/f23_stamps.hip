@@ -16,7 +16,8 @@ struct Layer { const char* name; int I, O, H; };
 int main(int argc, char** argv) {
     if (argc > 1) sg3::f23_force_rows(atoi(argv[1]));
     const int N = 8;
-    const Layer layers[] = {{"L5 512->512 @84", 512, 512, 84}, {"L6 512->512 @148", 512, 512, 148}, {"L8 323->203 @276", 323, 203, 276}, {"L9 203->128 @532", 203, 128, 532}};
+    const Layer layers[] = {{"L5 512->512 @84", 512, 512, 84}, {"L6 512->512 @148", 512, 512, 148}, {"L8 323->203 @276", 323, 203, 276}, {"L9 203->128 @532", 203, 128, 532},
+                            {"L10 128->81 @534", 128, 81, 534}, {"L11 81->51 @1046", 81, 51, 1046}};
     size_t maxIn = 0, maxOut = 0, maxW = 0;
     for (const Layer& L : layers) {
         maxIn = std::max(maxIn, (size_t)N * L.I * L.H * L.H); maxOut = std::max(maxOut, (size_t)N * L.O * (L.H + 2) * (L.H + 2));
