@@ -80,7 +80,7 @@ input_transform_kernel(sg3_input_transform_params p) {
     const float g1 = __builtin_fmaf(f1, m[4], f0 * m[1]);
     const float nrm = sqrtf(g0 * g0 + g1 * g1);
     float amp = 1.f - (nrm - p.bandwidth) / (p.samplingRate / 2.f - p.bandwidth);
-    amp = fminf(fmaxf(amp, 0.f), 1.f);
+    amp = amp < 0.f ? 0.f : (amp > 1.f ? 1.f : amp);       // torch.clamp: a NaN (|t[:2]| = 0) stays one; fminf / fmaxf would return the bound
     const size_t o = (size_t)n * p.C + c;
     p.outFreqs[2 * o] = g0; p.outFreqs[2 * o + 1] = g1;
     p.outPhases[o] = ph;

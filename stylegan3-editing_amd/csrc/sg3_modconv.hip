@@ -1176,6 +1176,9 @@ static __device__ __forceinline__ void prep_s_body(const sg3_modconv_prep_params
         int e = 0;
         if (peak > 0.f && peak < 3.0e38f) e = (int)ceilf(log2f(peak / 32768.f));    // either direction: tiny operands (gradients) are scaled up
         if (p.precision == SG3_CONV_F16X3_F23 || p.precision == SG3_CONV_F16_F23) e += 1;                               // the input transform forms sums of two samples
+        // both factors stay normal floats: a peak of 2^-113 or less (a gradient that has almost underflowed) would make `down` 2^128 = inf and
+        // the convolution 0 * inf.  sIn * dcoef is unchanged; the operands then peak below 2^15 by the exponents held back
+        e = min(max(e, -126), 126);
         down = ldexpf(1.f, -e); up = ldexpf(1.f, e);
     }
     __syncthreads();

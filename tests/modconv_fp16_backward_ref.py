@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 import modconv_backward_ref as R
+import style_stage_ref as S
 
 MAGNITUDES = (2.0 ** -20, 2.0 ** -10, 1.0, 2.0 ** 10)      # max |dy| of the sweep
 F16_MAX_REL, F16_MEAN_REL = 4e-3, 4e-4                    # modconv_abi.bounds of the single-product forms
@@ -150,23 +151,12 @@ def style_grad_refs(x, dy, w, s, demodulate, input_gain, k, pad, x_amax, dy_amax
 
 def _input_fp64(inp, t):
     """SynthesisInput.forward (reference networks_stylegan3.py:204-244) on float64 parameters and t [N,4] float64."""
-    n = t.shape[0]
-    eye = torch.eye(3, dtype=torch.float64, device=t.device)
-    rows = lambda a, b, c: torch.stack([a, b, c], dim=1)          # noqa: E731
-    one, zero = torch.ones_like(t[:, 0]), torch.zeros_like(t[:, 0])
-    rot = torch.stack([rows(t[:, 0], -t[:, 1], zero), rows(t[:, 1], t[:, 0], zero), rows(zero, zero, one)], dim=1)
-    trans = torch.stack([rows(one, zero, -t[:, 2]), rows(zero, one, -t[:, 3]), rows(zero, zero, one)], dim=1)
-    m = rot @ trans @ inp.transform.to(torch.float64)
-    freqs = inp.freqs.to(torch.float64).unsqueeze(0)
-    phases = inp.phases.to(torch.float64).unsqueeze(0) + (freqs @ m[:, :2, 2:]).squeeze(2)
-    freqs = freqs @ m[:, :2, :2]
-    amps = (1 - (freqs.norm(dim=2) - inp.bandwidth) / (inp.sampling_rate / 2 - inp.bandwidth)).clamp(0, 1)
-    theta = eye[:2].clone()
+    freqs, phases, amps = S.input_transform_chain(t, inp.transform, inp.freqs, inp.phases, inp.bandwidth, inp.sampling_rate, False)
+    theta = torch.eye(3, dtype=torch.float64, device=t.device)[:2].clone()
     theta[0, 0] = 0.5 * inp.size[0] / inp.sampling_rate
     theta[1, 1] = 0.5 * inp.size[1] / inp.sampling_rate
     grid = torch.nn.functional.affine_grid(theta.unsqueeze(0), [1, 1, int(inp.size[1]), int(inp.size[0])], align_corners=False)
-    x = (grid.unsqueeze(3) @ freqs.permute(0, 2, 1).unsqueeze(1).unsqueeze(2)).squeeze(3)
-    x = torch.sin((x + phases.unsqueeze(1).unsqueeze(2)) * (np.pi * 2)) * amps.unsqueeze(1).unsqueeze(2)
+    x = S.fourier_chain(grid[0], freqs, phases, amps).permute(0, 2, 3, 1)
     return (x @ (inp.weight / np.sqrt(inp.channels)).t()).permute(0, 3, 1, 2)
 
 
