@@ -145,6 +145,34 @@ SG3_API int sg3_filtered_lrelu_force_up4_wide(int wide);
 SG3_API int sg3_filtered_lrelu_stream_grid(const sg3_filtered_lrelu_params* p, int* nStrips, int* stripW, int* nFullStrips, int* nChunks,
                                            int* chunkRows);
 
+/* kinds of launch of sg3_filtered_lrelu */
+enum {
+    SG3_FLRELU_NONE      = 0,   /* no fused kernel (SG3_NO_KERNEL) */
+    SG3_FLRELU_POINTWISE = 1,   /* flrelu_pointwise_kernel<T>: up = down = 1, 1x1 filters; totalBlocks[0] workgroups of 256 */
+    SG3_FLRELU_STREAM    = 2,   /* flrelu_stream_kernel<T, U, D, VPH, RADIAL, SIGNS, G, WIDE>: workgroups of one wave */
+};
+
+/* What sg3_filtered_lrelu launches for a call: the kind, and per launch ([0], and [1] of the two-launch mixed form) the template
+ * coordinates of the streaming kernel and its work decomposition. */
+typedef struct sg3_filtered_lrelu_dispatch_info {
+    int32_t        kind;          /* SG3_FLRELU_* */
+    int32_t        launches;      /* 1 | 2; 0: none, or a grid that would pass 2^31 - 1 workgroups (SG3_BAD_ARG) */
+    int32_t        planesPerWave; /* sg3_filtered_lrelu_planes_per_wave */
+    int32_t        nChunks, chunkRows; /* output rows: nChunks chunks of chunkRows rows, both launches */
+    int32_t        sumSlots;      /* readSigns calls: ySumPartial / yAbsMaxPartial values per plane (sg3_filtered_lrelu_sum_slots), else 0 */
+    int32_t        fastAct;       /* 1: the plain forward tries the one-instruction activation first */
+    int32_t        U[2], D[2], VPH[2], RADIAL[2], SIGNS[2], G[2], WIDE[2];
+    int32_t        nStrips[2], TW[2];  /* strips of TW output columns */
+    int32_t        ox0Base[2];    /* first output column of the two-plane strip */
+    int32_t        wideBlocks[2]; /* G = 2: leading workgroups that take one plane each, on the full strips */
+    int32_t        totalBlocks[2]; /* the grid */
+} sg3_filtered_lrelu_dispatch_info;
+
+/* The plan of a call, from the function the launch itself uses (host only: no launch, no pointer followed -- only whether s is set
+ * and the alignment of 2-D taps is read, so placeholders do; x, y, fu and fd may be NULL).  Returns what sg3_filtered_lrelu would
+ * return before launching: SG3_OK, SG3_NO_KERNEL, or SG3_BAD_ARG for a call it rejects. */
+SG3_API int sg3_filtered_lrelu_dispatch(const sg3_filtered_lrelu_params* p, sg3_filtered_lrelu_dispatch_info* out);
+
 /* host-only: the bound on |input + bias| under which the plain forward's streaming kernel evaluates lrelu + clamp as one
  * med3(u, slope*u, clamp/gain) -- the same computation the kernel makes from the separable up filter fu (fuW taps, HOST
  * memory here).  -1 when there is none (clamp/gain not positive). */

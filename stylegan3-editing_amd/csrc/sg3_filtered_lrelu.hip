@@ -42,10 +42,9 @@
 // the caller composes upfirdn2d + filtered_lrelu_act + upfirdn2d, exactly like the reference's rc = -1 path.
 //
 // Algorithmic traffic: C*(xH*xW + yH*yW)*sizeof(T) bytes per image -- the roofline figure bench.py uses.
-#include "sg3_common.h"
+#include "sg3_flrelu_plan.h"
 #include <atomic>
-#include <cmath>
-#include <cstdlib>
+#include <utility>
 
 // rows of input the streaming kernel keeps in flight per wave (each costs NL registers per lane): three rows are ~3 x 1.5 us
 // of work, several HBM latencies
@@ -248,24 +247,7 @@ __device__ __forceinline__ v2f up2d_pair(const TapRow& t, int s) {
     return (j & 1) ? (v2f){v.z, v.w} : (v2f){v.x, v.y};
 }
 
-template <int U, int D> struct StreamCfg {
-    static constexpr int FU = 6 * U, FD = 6 * D;
-    static constexpr int CPL = 4;                       // upsampled columns per lane
-    static constexpr int GROUPS = CPL / U;              // column groups per lane that share one input window
-    static constexpr int IWS = GROUPS * 64 + 6;         // input samples a wave needs per row (+ slack)
-    static constexpr int NL = (IWS + 63) / 64;          // global loads per lane per row
-    static constexpr int SIN = NL * 64;                 // LDS floats for the input row
-    static constexpr int SOUT = 4 + 256 + 32;           // LDS floats for the output row (+ read-ahead of the last lanes)
-    static constexpr int MAXTW = (256 - FD) / D;        // output columns a wave's 256 upsampled columns can complete
-    // packed mode (two narrow planes per wave, 32 lanes each): input-row / output-row LDS segment of one plane, and the widest
-    // output 32 lanes complete
-    static constexpr int PSEG = GROUPS * 32 + 8;        // 72 (up 2) | 40 (up 4) input samples; 2 PSEG <= SIN
-    static constexpr int POSEG = 4 * 32 + 16;           // 144 floats; 2 POSEG <= SOUT
-    // output column 2l + 1 reads the exchanged row up to slot 4 + 4l + 13, and the 32 lanes write slots 4 - delta .. 131 - delta
-    // (delta <= 3): l <= 26
-    static constexpr int PACKTW = 2 * 27;               // 54 output columns (down 2)
-    static_assert(2 * PSEG <= SIN && 2 * POSEG <= SOUT, "packed LDS rows fit the unpacked ones");
-};
+// StreamCfg<U, D>, the tile constants of the streaming kernel: sg3_flrelu_plan.h (the launch plan reads MAXTW and PACKTW)
 
 // element <-> fp32 through raw buffer instructions: the hardware range check (offset >= num_records reads 0 /
 // drops the store) replaces every per-lane bounds branch
@@ -1045,86 +1027,12 @@ flrelu_pointwise_kernel(PointParams p) {
 }
 
 // ---------------------------------------------------------------------------
-static bool stream_supported(int up, int down, int fuW, int fuH, int fdW, int fdH) {
-    if (fuH == 12) {
-        // adjoint of the radial (config R) layers: 12x12 up filter, up 2, separable down 2 (12 taps) or 4 (24 taps)
-        return up == 2 && fuW == 12 && fdH == 0 && ((down == 2 && fdW == 12) || (down == 4 && fdW == 24));
-    }
-    if (fuH != 0) return false;                               // otherwise a separable up filter
-    if (fdH != 0 && fdH != 12) return false;                  // separable, or full 12x12 (radial) down filter
-    if (down == 2 && fdW == 12) return (up == 2 && fuW == 12) || (up == 4 && fuW == 24);
-    // adjoint of the up-4 layers: up 2 (12 taps), down 4 (24 taps), separable
-    return down == 4 && fdW == 24 && fdH == 0 && up == 2 && fuW == 12;
-}
-
-// the streaming kernel evaluates lrelu as max(v, slope * v), valid for 0 <= slope <= 1 (every StyleGAN3 layer)
-static bool stream_params_ok(const sg3_filtered_lrelu_params& q) {
-    if (q.fdH != 0 && ((uintptr_t)q.fd & 15) != 0) return false;  // 2-D taps are fetched as 16-byte scalar quads
-    if (q.fuH != 0 && (((uintptr_t)q.fu & 15) != 0 || !q.readSigns)) return false;       // 2-D up filter: adjoint passes only
-    const bool signs = q.writeSigns || q.readSigns;
-    if (signs && (!q.s || q.sH <= 0 || q.sWbytes <= 0)) return false;
-    if (q.readSigns && q.fdH != 0) return false;                                          // adjoint passes: separable down filter
-    if (q.readSigns && q.up != 2) return false;                                            // adjoint passes upsample by 2
-    if (q.down == 4 && !q.readSigns) return false;                                         // down 4 exists for the adjoint only
-    return q.slope >= 0.f && q.slope <= 1.f && q.xStride[3] == 1 && q.yStride[3] == 1 && !(q.clamp < 0.f);
-}
-
-static bool pointwise_supported(int up, int down, int fuW, int fuH, int fdW, int fdH) {
-    return up == 1 && down == 1 && fuW == 1 && fdW == 1 && fuH <= 1 && fdH <= 1;
-}
-
-// Work decomposition of the streaming kernel: strips of equal width, as wide as a wave's 256 upsampled columns can complete
-// (120 for down 2, 58 for down 4); row chunks: enough waves to fill 256 CUs x 16 waves a few times over, but chunks tall
-// enough that the 11-row warm-up stays small.
-static void stream_grid(int N, int C, int yH, int yW, int down, int& nStrips, int& TW, int& nChunks, int& CH) {
-    const int maxTW = (256 - 6 * down) / down;
-    nStrips = ceil_div(yW, maxTW);
-    TW = ceil_div(yW, nStrips);
-    const long long planes = (long long)N * C;
-    const long long wantWaves = 256LL * 16 * 4;
-    int n = (int)ceil_div64(wantWaves, planes * nStrips);
-    const int maxChunks = max(1, yH / 48);
-    if (n > maxChunks) n = maxChunks;
-    if (n < 1) n = 1;
-    CH = ceil_div(yH, n);
-    nChunks = ceil_div(yH, CH);
-}
-
-// Two planes per wave (packed mode of the streaming kernel) for the plain forward on strips at most `width` columns wide: dense
-// (n, c) planes (the second plane of a wave sits one channel stride after the first), offsets inside a 2 GB descriptor.
-// SG3_FLRELU_NOPACK=1 in the environment keeps one plane per wave (A/B timing; read once).
-static bool stream_packs_planes(const sg3_filtered_lrelu_params& q, int width) {
-    static const bool allowed = [] { const char* e = getenv("SG3_FLRELU_NOPACK"); return !(e && e[0] == '1'); }();
-    const long long esz = q.dtype == SG3_F32 ? 4 : 2;
-    const long long xsC = q.xStride[1], ysC = q.yStride[1];
-    return allowed && !q.readSigns && !q.writeSigns && q.down == 2 && width <= StreamCfg<2, 2>::PACKTW &&
-           q.xStride[0] == (long long)q.C * xsC && q.yStride[0] == (long long)q.C * ysC && xsC > 0 && ysC > 0 &&
-           (xsC + q.xW) * esz < 0x7fffffffLL && (ysC + q.yW) * esz < 0x7fffffffLL;
-}
-
-// The one-instruction activation of the plain forward (StreamParams.fastAct): for a finite positive gain and a clamp that is a number.
-// SG3_FLRELU_SLOWACT=1 in the environment keeps lrelu + clamp everywhere (A/B timing and the parity tests; read on every call, so
-// that a test can compare both forms in one process).
-static bool stream_fast_activation(const sg3_filtered_lrelu_params& q) {
-    const char* e = getenv("SG3_FLRELU_SLOWACT");
-    return !(e && e[0] == '1') && !q.readSigns && !q.writeSigns && q.gain > 0.f && q.gain < INFINITY && q.clamp >= 0.f;
-}
-
+// Which kernel, how many launches and what grid a call takes: plan_filtered_lrelu, sg3_flrelu_plan.h.
+//
 // The up-4 separable plain forward has two forms that compute the same thing bit for bit: the default (up taps placed by hand, at
 // most 128 VGPRs, four waves per SIMD) and the earlier one (`Stream`'s WIDE).  A process setting, seeded ONCE from the environment
 // (SG3_FLRELU_UP4_WIDE=1: A/B timing) and changed only by an explicit sg3_filtered_lrelu_force_up4_wide call (the bit-identity test).
 static std::atomic<int> g_up4_wide{[] { const char* e = getenv("SG3_FLRELU_UP4_WIDE"); return (e && e[0] == '1') ? 1 : 0; }()};
-static bool stream_up4_wide(const sg3_filtered_lrelu_params& q) {
-    return q.up == 4 && q.fdH == 0 && !q.readSigns && !q.writeSigns && g_up4_wide.load(std::memory_order_relaxed) != 0;
-}
-
-// width of the full strips when a row is cut into full strips + a packed remainder, and their number (0: equal strips instead --
-// no remainder, a remainder too wide to pack, or more waves than equal strips take)
-constexpr int STREAM_FULL_TW = 120;
-static int stream_full_strips(int yW, int nStripsEqual) {
-    const int nFull = (yW - 1) / STREAM_FULL_TW, rem = yW - nFull * STREAM_FULL_TW;
-    return (nFull >= 1 && nFull + 1 == nStripsEqual && rem <= StreamCfg<2, 2>::PACKTW) ? nFull : 0;
-}
 
 // The per-workgroup partial sums / maxima an adjoint launch left ([N][C][slots] each) -> the bias gradient db[c] = sum over (n, slot)
 // and max |dx| = max over everything, in one small launch (as torch ops: a strided reduction and a max, ~19 us per layer and PTI step).
@@ -1153,8 +1061,45 @@ flrelu_finish_partials_kernel(const float* __restrict__ psum, const float* __res
     if (threadIdx.x == 0) amax[0] = __builtin_fmaxf(__builtin_fmaxf(red[0], red[1]), __builtin_fmaxf(red[2], red[3]));
 }
 
+typedef void (*StreamKernel)(StreamParams);
+
+// The kernel of one plan entry: the 82 instantiations per tensor type, nullptr for coordinates none of them has.
+template <typename T, int U, int D, int R, int S, int G, int W, int... V>
+static StreamKernel stream_kernel_vph(int vph, std::integer_sequence<int, V...>) {
+    StreamKernel f = nullptr;
+    ((vph == V ? (void)(f = flrelu_stream_kernel<T, U, D, V, R, S, G, W>) : (void)0), ...);
+    return f;
+}
+template <typename T, int U, int D, int S, int G, class VS, int... R>
+static StreamKernel stream_kernel_radial(int radial, int vph, VS vs, std::integer_sequence<int, R...>) {
+    StreamKernel f = nullptr;
+    ((radial == R ? (void)(f = stream_kernel_vph<T, U, D, R, S, G, 0>(vph, vs)) : (void)0), ...);
+    return f;
+}
 template <typename T>
-static int launch_stream(const sg3_filtered_lrelu_params& q, hipStream_t st) {
+static StreamKernel stream_kernel(const FlreluPlan& pl, int i) {
+    typedef std::integer_sequence<int, 0, 1> V2;
+    typedef std::integer_sequence<int, 0, 1, 2, 3> V4;
+    typedef std::integer_sequence<int, 0, 1, 2, 5, 6> Forward;     // separable | 12x12 | 12x12 flipped | 12x12 with mirror-symmetric rows | the same, flipped
+    typedef std::integer_sequence<int, 0, 3, 4> Adjoint;           // separable | 12x12 up filter | the same, flipped
+    const int U = pl.U[i], D = pl.D[i], V = pl.VPH[i], R = pl.RADIAL[i], S = pl.SIGNS[i], G = pl.G[i];
+    if (pl.WIDE[i]) {                                              // the earlier form of the up-4 separable plain forward
+        if (U != 4 || D != 2 || R != 0 || S != 0) return nullptr;
+        return G == 1 ? stream_kernel_vph<T, 4, 2, 0, 0, 1, 1>(V, V2()) : G == 2 ? stream_kernel_vph<T, 4, 2, 0, 0, 2, 1>(V, V2()) : nullptr;
+    }
+    if (S == 2) {                                                  // adjoint: up 2, one plane per wave
+        if (U != 2 || G != 1) return nullptr;
+        return D == 2 ? stream_kernel_radial<T, 2, 2, 2, 1>(R, V, V2(), Adjoint()) : D == 4 ? stream_kernel_radial<T, 2, 4, 2, 1>(R, V, V4(), Adjoint()) : nullptr;
+    }
+    if (D != 2 || (U != 2 && U != 4)) return nullptr;
+    if (S == 1 && G == 1) return U == 2 ? stream_kernel_radial<T, 2, 2, 1, 1>(R, V, V2(), Forward()) : stream_kernel_radial<T, 4, 2, 1, 1>(R, V, V2(), Forward());
+    if (S == 0 && G == 1) return U == 2 ? stream_kernel_radial<T, 2, 2, 0, 1>(R, V, V2(), Forward()) : stream_kernel_radial<T, 4, 2, 0, 1>(R, V, V2(), Forward());
+    if (S == 0 && G == 2) return U == 2 ? stream_kernel_radial<T, 2, 2, 0, 2>(R, V, V2(), Forward()) : stream_kernel_radial<T, 4, 2, 0, 2>(R, V, V2(), Forward());
+    return nullptr;
+}
+
+template <typename T>
+static int launch_stream(const sg3_filtered_lrelu_params& q, const FlreluPlan& pl, hipStream_t st) {
     StreamParams p;
     p.x = q.x; p.y = q.y; p.b = q.b; p.fu = q.fu; p.fd = q.fd;
     p.C = q.C; p.planes = q.N * q.C; p.xH = q.xH; p.xW = q.xW; p.yH = q.yH; p.yW = q.yW;
@@ -1163,7 +1108,7 @@ static int launch_stream(const sg3_filtered_lrelu_params& q, hipStream_t st) {
     p.bStride = q.bStride;
     p.px0 = q.px0; p.py0 = q.py0;
     p.gain = q.gain; p.slope = q.slope; p.clamp = q.clamp; p.flip = q.flip;
-    p.fastAct = stream_fast_activation(q) ? 1 : 0;
+    p.fastAct = pl.fastAct;
 
     p.s = q.s; p.sH = q.sH; p.sWb = q.sWbytes; p.sx = q.sx; p.sy = q.sy;
     p.ysum = q.ySumPartial;
@@ -1171,110 +1116,30 @@ static int launch_stream(const sg3_filtered_lrelu_params& q, hipStream_t st) {
 #ifdef SG3_STAMPS
     p.stamps = g_stamps;
 #endif
-    stream_grid(q.N, q.C, q.yH, q.yW, q.down, p.nStrips, p.TW, p.nChunks, p.CH);
-    const long long planes = (long long)q.N * q.C;
-    const long long total = planes * p.nStrips * p.nChunks;
-    if (total > 0x7fffffffLL) { set_error("filtered_lrelu: grid too large"); return SG3_BAD_ARG; }
-    p.totalBlocks = (int)total;
-
-    p.ox0Base = 0;
-    const bool packed = p.nStrips == 1 && stream_packs_planes(q, q.yW);    // the 36^2 .. 52^2 layers
-    if (packed) p.totalBlocks = (int)((planes + 1) / 2 * p.nChunks);
-    // Rows a little wider than a whole number of full strips (148 = 120 + 28, 276 = 2 x 120 + 36, 532 = 4 x 120 + 52 columns: the
-    // 148^2 .. 532^2 layers): equal strips would leave 40 .. 57 of a wave's 64 lanes at work.  Instead the full-width strips go
-    // first, one plane per wave, and the remainder strip follows in a second launch with two planes per wave:
-    // nFull + 1/2 waves per plane and row chunk instead of nFull + 1.
-    const int remFull = stream_full_strips(q.yW, p.nStrips);
-    const bool mixed = !packed && remFull > 0 && stream_packs_planes(q, q.yW - remFull * STREAM_FULL_TW);
-    // ONE launch of the two-plane kernel, whose first blocks take the full strips, where it holds as many waves per SIMD as the
-    // one-plane kernel (separable: 120 / 124 registers at up 2, 104 / 111 at up 4 -- 142 / 147 in the WIDE form; 12x12 down filter at up 4: 153 .. 160 against
-    // 148 .. 156, three waves either way).  12x12 down filter at up 2: two launches (135 registers against 128: three waves, not four)
-    const bool oneLaunch = mixed && (q.fdH == 0 || q.up == 4);
-    p.wideBlocks = 0;
-    if (mixed) {
-        p.nStrips = remFull; p.TW = STREAM_FULL_TW;
-        p.totalBlocks = (int)(planes * remFull * p.nChunks);
-        if (oneLaunch) {
-            p.wideBlocks = p.totalBlocks;
-            p.ox0Base = remFull * STREAM_FULL_TW;
-            const long long all = (long long)p.totalBlocks + (planes + 1) / 2 * p.nChunks;
-            if (all > 0x7fffffffLL) { set_error("filtered_lrelu: grid too large"); return SG3_BAD_ARG; }
-            p.totalBlocks = (int)all;
+    p.nChunks = pl.nChunks; p.CH = pl.chunkRows;
+    for (int i = 0; i < pl.launches; i++) {
+        p.nStrips = pl.nStrips[i]; p.TW = pl.TW[i]; p.ox0Base = pl.ox0Base[i]; p.wideBlocks = pl.wideBlocks[i]; p.totalBlocks = pl.totalBlocks[i];
+        const StreamKernel kernel = stream_kernel<T>(pl, i);
+        if (!kernel) {
+            set_error("filtered_lrelu: no flrelu_stream_kernel<U=%d, D=%d, VPH=%d, RADIAL=%d, SIGNS=%d, G=%d, WIDE=%d>", pl.U[i], pl.D[i], pl.VPH[i],
+                      pl.RADIAL[i], pl.SIGNS[i], pl.G[i], pl.WIDE[i]);
+            return SG3_NO_KERNEL;
         }
+        hipLaunchKernelGGL(kernel, dim3((unsigned)p.totalBlocks), dim3(64), 0, st, p);
+        SG3_LAUNCH_CHECK("flrelu_stream_kernel");
     }
-
-    const int vph = (((q.py0 - (q.up - 1)) % q.down) + q.down) % q.down;
-    const bool up4Wide = stream_up4_wide(q);
-    dim3 g((unsigned)p.totalBlocks), b(64);
-#define SG3_UP4_WIDE_LAUNCH(GG) do { \
-        if (vph == 0) hipLaunchKernelGGL((flrelu_stream_kernel<T, 4, 2, 0, 0, 0, GG, 1>), g, b, 0, st, p); \
-        else hipLaunchKernelGGL((flrelu_stream_kernel<T, 4, 2, 1, 0, 0, GG, 1>), g, b, 0, st, p); } while (0)
-#define SG3_STREAM_LAUNCH(U, D, V, R, S) hipLaunchKernelGGL((flrelu_stream_kernel<T, U, D, V, R, S>), g, b, 0, st, p)
-#define SG3_STREAM_LAUNCH_V(U, R, S) do { if (vph == 0) SG3_STREAM_LAUNCH(U, 2, 0, R, S); else SG3_STREAM_LAUNCH(U, 2, 1, R, S); } while (0)
-#define SG3_PACKED_LAUNCH(U, V, R) hipLaunchKernelGGL((flrelu_stream_kernel<T, U, 2, V, R, 0, 2>), g, b, 0, st, p)
-#define SG3_PACKED_LAUNCH_V(U, R) do { if (vph == 0) SG3_PACKED_LAUNCH(U, 0, R); else SG3_PACKED_LAUNCH(U, 1, R); } while (0)
-#define SG3_PACKED_UP(U) do { switch (variant) { \
-        case 0: SG3_PACKED_LAUNCH_V(U, 0); break; case 1: SG3_PACKED_LAUNCH_V(U, 1); break; \
-        case 2: SG3_PACKED_LAUNCH_V(U, 2); break; case 5: SG3_PACKED_LAUNCH_V(U, 5); break; \
-        default: SG3_PACKED_LAUNCH_V(U, 6); break; } } while (0)
-    // separable | 12x12 | 12x12 flipped | 12x12 with mirror-symmetric rows | the same, flipped
-    const int variant = q.fdH == 0 ? 0 : (q.fdMirror ? (q.flip ? 6 : 5) : (q.flip ? 2 : 1));
-#define SG3_FORWARD_UP(U, S) do { switch (variant) { \
-        case 0: SG3_STREAM_LAUNCH_V(U, 0, S); break; case 1: SG3_STREAM_LAUNCH_V(U, 1, S); break; \
-        case 2: SG3_STREAM_LAUNCH_V(U, 2, S); break; case 5: SG3_STREAM_LAUNCH_V(U, 5, S); break; \
-        default: SG3_STREAM_LAUNCH_V(U, 6, S); break; } } while (0)
-#define SG3_FORWARD_LAUNCH(S) do { if (q.up == 2) SG3_FORWARD_UP(2, S); else SG3_FORWARD_UP(4, S); } while (0)
-    if (q.readSigns) {
-#define SG3_ADJOINT_LAUNCH(R) do { \
-        if (q.down == 2) SG3_STREAM_LAUNCH_V(2, R, 2); \
-        else switch (vph) { \
-            case 0: SG3_STREAM_LAUNCH(2, 4, 0, R, 2); break; \
-            case 1: SG3_STREAM_LAUNCH(2, 4, 1, R, 2); break; \
-            case 2: SG3_STREAM_LAUNCH(2, 4, 2, R, 2); break; \
-            default: SG3_STREAM_LAUNCH(2, 4, 3, R, 2); break; \
-        } } while (0)
-        if (q.fuH == 0) SG3_ADJOINT_LAUNCH(0);
-        else if (q.flip) SG3_ADJOINT_LAUNCH(4);
-        else SG3_ADJOINT_LAUNCH(3);
-#undef SG3_ADJOINT_LAUNCH
-    } else if (q.writeSigns) {
-        SG3_FORWARD_LAUNCH(1);
-    } else if (packed || oneLaunch) {
-        if (up4Wide) SG3_UP4_WIDE_LAUNCH(2); else if (q.up == 2) SG3_PACKED_UP(2); else SG3_PACKED_UP(4);
-    } else {
-        if (up4Wide) SG3_UP4_WIDE_LAUNCH(1); else SG3_FORWARD_LAUNCH(0);
-        if (mixed) {
-            SG3_LAUNCH_CHECK("flrelu_stream_kernel");
-            p.ox0Base = remFull * STREAM_FULL_TW; p.nStrips = 1; p.TW = q.yW - p.ox0Base;
-            p.totalBlocks = (int)((planes + 1) / 2 * p.nChunks);
-            g = dim3((unsigned)p.totalBlocks);
-            if (up4Wide) SG3_UP4_WIDE_LAUNCH(2); else if (q.up == 2) SG3_PACKED_UP(2); else SG3_PACKED_UP(4);
-        }
-    }
-#undef SG3_UP4_WIDE_LAUNCH
-#undef SG3_PACKED_UP
-#undef SG3_PACKED_LAUNCH_V
-#undef SG3_PACKED_LAUNCH
-#undef SG3_FORWARD_LAUNCH
-#undef SG3_FORWARD_UP
-#undef SG3_STREAM_LAUNCH_V
-#undef SG3_STREAM_LAUNCH
-    SG3_LAUNCH_CHECK("flrelu_stream_kernel");
     return SG3_OK;
 }
 
 template <typename T>
-static int launch_pointwise(const sg3_filtered_lrelu_params& q, hipStream_t st) {
+static int launch_pointwise(const sg3_filtered_lrelu_params& q, const FlreluPlan& pl, hipStream_t st) {
     PointParams p;
     p.x = q.x; p.y = q.y; p.b = q.b; p.fu = q.fu; p.fd = q.fd;
     p.N = q.N; p.C = q.C; p.H = q.xH; p.W = q.xW; p.yH = q.yH; p.yW = q.yW;
     for (int i = 0; i < 4; i++) { p.xs[i] = q.xStride[i]; p.ys[i] = q.yStride[i]; }
     p.bStride = q.bStride; p.px0 = q.px0; p.py0 = q.py0;
     p.gain = q.gain; p.slope = q.slope; p.clamp = q.clamp;
-    const long long total = (long long)q.N * q.C * q.yH * q.yW;
-    long long blocks = ceil_div64(total, 256);
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL((flrelu_pointwise_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((flrelu_pointwise_kernel<T>), dim3((unsigned)pl.totalBlocks[0]), dim3(256), 0, st, p);
     SG3_LAUNCH_CHECK("flrelu_pointwise_kernel");
     return SG3_OK;
 }
@@ -1338,52 +1203,57 @@ float sg3_filtered_lrelu_fast_threshold(const float* fu, int fuW, int up, float 
 
 int sg3_filtered_lrelu_force_up4_wide(int wide) { return sg3::g_up4_wide.exchange(wide ? 1 : 0); }
 
+// the plan of a call the older queries answer for: a tensor type the kernels have and a non-empty output, nothing else checked
+static bool query_plan(const sg3_filtered_lrelu_params* p, sg3::FlreluPlan& pl) {
+    if (!p || (p->dtype != SG3_F32 && p->dtype != SG3_F16) || p->N <= 0 || p->C <= 0 || p->yH <= 0 || p->yW <= 0) return false;
+    pl = sg3::plan_filtered_lrelu(*p, sg3::FlreluKnobs::env(), sg3::g_up4_wide.load(std::memory_order_relaxed));
+    return pl.kind == SG3_FLRELU_STREAM;
+}
+
 int sg3_filtered_lrelu_planes_per_wave(const sg3_filtered_lrelu_params* p) {
-    using namespace sg3;
-    if (!p || (p->dtype != SG3_F32 && p->dtype != SG3_F16)) return 0;
-    const bool signs = p->writeSigns || p->readSigns;
-    if (!signs && pointwise_supported(p->up, p->down, p->fuW, p->fuH, p->fdW, p->fdH)) return 0;
-    if (!(stream_supported(p->up, p->down, p->fuW, p->fuH, p->fdW, p->fdH) && stream_params_ok(*p))) return 0;
-    if (p->N <= 0 || p->C <= 0 || p->yH <= 0 || p->yW <= 0) return 0;
-    int nStrips, TW, nChunks, CH;
-    stream_grid(p->N, p->C, p->yH, p->yW, p->down, nStrips, TW, nChunks, CH);
-    if (nStrips == 1) return stream_packs_planes(*p, p->yW) ? 2 : 1;
-    const int nFull = stream_full_strips(p->yW, nStrips);
-    return (nFull > 0 && stream_packs_planes(*p, p->yW - nFull * STREAM_FULL_TW)) ? 3 : 1;
+    sg3::FlreluPlan pl;
+    return query_plan(p, pl) ? pl.planesPerWave : 0;
 }
 
 int sg3_filtered_lrelu_stream_grid(const sg3_filtered_lrelu_params* p, int* nStrips, int* stripW, int* nFullStrips, int* nChunks, int* chunkRows) {
-    using namespace sg3;
-    if (sg3_filtered_lrelu_planes_per_wave(p) == 0) return 0;           // not a streaming-kernel call
-    int ns, tw, nc, ch;
-    stream_grid(p->N, p->C, p->yH, p->yW, p->down, ns, tw, nc, ch);
-    // the cut `launch_stream` makes: full 120-column strips + a two-plane remainder strip where that applies, equal strips otherwise
-    const int nFull = (ns > 1 && stream_packs_planes(*p, p->yW - stream_full_strips(p->yW, ns) * STREAM_FULL_TW)) ? stream_full_strips(p->yW, ns) : 0;
-    if (nStrips) *nStrips = ns;
-    if (stripW) *stripW = nFull > 0 ? STREAM_FULL_TW : tw;
-    if (nFullStrips) *nFullStrips = nFull;
-    if (nChunks) *nChunks = nc;
-    if (chunkRows) *chunkRows = ch;
+    sg3::FlreluPlan pl;
+    if (!query_plan(p, pl)) return 0;                                   // not a streaming-kernel call
+    const bool mixed = pl.planesPerWave == 3;                           // launch 0 takes the full strips, one more strip follows them
+    if (nStrips) *nStrips = pl.nStrips[0] + (mixed ? 1 : 0);
+    if (stripW) *stripW = pl.TW[0];
+    if (nFullStrips) *nFullStrips = mixed ? pl.nStrips[0] : 0;
+    if (nChunks) *nChunks = pl.nChunks;
+    if (chunkRows) *chunkRows = pl.chunkRows;
     return 1;
 }
 
-int sg3_filtered_lrelu(const sg3_filtered_lrelu_params* p, void* stream) {
+int sg3_filtered_lrelu_dispatch(const sg3_filtered_lrelu_params* p, sg3_filtered_lrelu_dispatch_info* out) {
     using namespace sg3;
-    SG3_REQUIRE(p && p->x && p->y && p->fu && p->fd, "filtered_lrelu: null tensor");
+    SG3_REQUIRE(p && out, "filtered_lrelu_dispatch: null argument");
     SG3_REQUIRE(p->N > 0 && p->C > 0 && p->xH > 0 && p->xW > 0, "filtered_lrelu: x is empty");
     SG3_REQUIRE(p->yH > 0 && p->yW > 0, "filtered_lrelu: output must be at least 1x1");
     SG3_REQUIRE(p->up >= 1 && p->down >= 1, "filtered_lrelu: up and down must be at least 1");
     SG3_REQUIRE(p->dtype == SG3_F32 || p->dtype == SG3_F16, "filtered_lrelu: x must be float16 or float32");
     SG3_REQUIRE(!(p->writeSigns && p->readSigns), "filtered_lrelu: cannot read and write signs in one call");
+    *out = plan_filtered_lrelu(*p, FlreluKnobs::env(), g_up4_wide.load(std::memory_order_relaxed));
+    if (out->kind == SG3_FLRELU_NONE) {
+        set_error("filtered_lrelu: no fused kernel for up=%d down=%d fu=%dx%d fd=%dx%d signs=%d", p->up, p->down,
+                  p->fuW, p->fuH, p->fdW, p->fdH, (int)(p->writeSigns || p->readSigns));
+        return SG3_NO_KERNEL;
+    }
+    SG3_REQUIRE(out->launches > 0, "filtered_lrelu: grid too large");
+    return SG3_OK;
+}
+
+int sg3_filtered_lrelu(const sg3_filtered_lrelu_params* p, void* stream) {
+    using namespace sg3;
+    SG3_REQUIRE(p && p->x && p->y && p->fu && p->fd, "filtered_lrelu: null tensor");
+    FlreluPlan pl;
+    const int rc = sg3_filtered_lrelu_dispatch(p, &pl);
+    if (rc != SG3_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const bool signs = p->writeSigns || p->readSigns;
-    if (!signs && pointwise_supported(p->up, p->down, p->fuW, p->fuH, p->fdW, p->fdH))
-        return p->dtype == SG3_F32 ? launch_pointwise<float>(*p, st) : launch_pointwise<_Float16>(*p, st);
-    if (stream_supported(p->up, p->down, p->fuW, p->fuH, p->fdW, p->fdH) && stream_params_ok(*p))
-        return p->dtype == SG3_F32 ? launch_stream<float>(*p, st) : launch_stream<_Float16>(*p, st);
-    set_error("filtered_lrelu: no fused kernel for up=%d down=%d fu=%dx%d fd=%dx%d signs=%d", p->up, p->down,
-              p->fuW, p->fuH, p->fdW, p->fdH, (int)signs);
-    return SG3_NO_KERNEL;
+    if (pl.kind == SG3_FLRELU_POINTWISE) return p->dtype == SG3_F32 ? launch_pointwise<float>(*p, pl, st) : launch_pointwise<_Float16>(*p, pl, st);
+    return p->dtype == SG3_F32 ? launch_stream<float>(*p, pl, st) : launch_stream<_Float16>(*p, pl, st);
 }
 
 } // extern "C"

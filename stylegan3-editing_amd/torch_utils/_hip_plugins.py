@@ -18,7 +18,8 @@ import torch
 from . import _sg3abi as abi
 
 INT_MAX = 2 ** 31 - 1
-stream_call_log = None          # set to a list to record, per filtered_lrelu call, its work decomposition (sg3_filtered_lrelu_stream_grid) and,
+stream_call_log = None          # set to a list to record, per filtered_lrelu call, its work decomposition (sg3_filtered_lrelu_stream_grid), its launch
+                                # plan (`plan`: sg3_filtered_lrelu_dispatch as a dict) and,
                                 # for adjoint calls, the per-workgroup partial sums / maxima (tests)
 planes_per_wave_log = None      # set to a list to record sg3_filtered_lrelu_planes_per_wave of every filtered_lrelu call
 
@@ -50,6 +51,39 @@ def _no_kernel(return_sum, return_amax=False):
         if return_amax:
             base = base + (None,)
     return base
+
+
+PLACEHOLDER = 16        # a non-null, 16-byte aligned address for host-only queries, which follow no pointer
+
+
+def filtered_lrelu_params(dtype, x_shape, y_hw, x_strides, y_strides, up, down, fu_wh, fd_wh, px0, py0, gain, slope, clamp, flip, write_signs=False,
+                          read_signs=False, s_hw=(0, 0), sx=0, sy=0, sw_limit=0, b_stride=1, fd_mirror=False, x=PLACEHOLDER, y=PLACEHOLDER, b=PLACEHOLDER,
+                          s=PLACEHOLDER, fu=PLACEHOLDER, fd=PLACEHOLDER):
+    """The parameter block of one sg3_filtered_lrelu call: `dtype` an SG3_F32 | SG3_F16 code, strides in elements, fu_wh / fd_wh = (taps
+    per row, rows; 0 rows = separable), s_hw = (rows, bytes per row) of the sign tensor.  The binding passes device addresses; the
+    host-only queries (sg3_filtered_lrelu_dispatch, _planes_per_wave, _stream_grid) do with the placeholders."""
+    p = abi.FilteredLreluParams()
+    signs = bool(read_signs or write_signs)
+    p.x, p.y, p.b = x, y, b
+    p.s = s if signs else None
+    p.fu, p.fd = fu, fd
+    p.dtype = dtype
+    p.N, p.C, p.xH, p.xW = (int(v) for v in x_shape)
+    p.yH, p.yW = int(y_hw[0]), int(y_hw[1])
+    p.xStride, p.yStride, p.bStride = (ctypes.c_int64 * 4)(*x_strides), (ctypes.c_int64 * 4)(*y_strides), int(b_stride)
+    p.up, p.down, p.fuW, p.fuH, p.fdW, p.fdH = int(up), int(down), int(fu_wh[0]), int(fu_wh[1]), int(fd_wh[0]), int(fd_wh[1])
+    p.px0, p.py0 = int(px0), int(py0)
+    p.sH, p.sWbytes = (int(s_hw[0]), int(s_hw[1])) if signs else (0, 0)
+    p.sx, p.sy, p.swLimit = int(sx), int(sy), int(sw_limit)
+    p.gain, p.slope, p.clamp = float(gain), float(slope), float(clamp)
+    p.flip, p.writeSigns, p.readSigns = int(bool(flip)), int(bool(write_signs)), int(bool(read_signs))
+    p.fdMirror = int(bool(fd_mirror))
+    return p
+
+
+def dense_strides(n, c, h, w):
+    """element strides of a contiguous [n, c, h, w] tensor"""
+    return (c * h * w, h * w, w, 1)
 
 
 class FilteredLreluPlugin:
@@ -105,21 +139,12 @@ class FilteredLreluPlugin:
             _require(s.shape[0] == N and s.shape[1] == C, 'signs must have same batch & channels as x')
         # fused kernels read taps with unit stride
         fu_c, fd_c = fu.contiguous(), fd.contiguous()
-        p = abi.FilteredLreluParams()
-        p.x, p.y, p.b = abi.ptr(x), abi.ptr(y), abi.ptr(b)
-        p.s = abi.ptr(s) if (readSigns or writeSigns) else None
-        p.fu, p.fd = abi.ptr(fu_c), abi.ptr(fd_c)
-        p.dtype = abi.dtype_code(x.dtype)
-        p.N, p.C, p.xH, p.xW, p.yH, p.yW = N, C, xH, xW, yH.value, yW.value
-        p.xStride, p.yStride, p.bStride = abi.strides4(x), abi.strides4(y), int(b.stride(0))
-        p.up, p.down, p.fuW, p.fuH, p.fdW, p.fdH = int(up), int(down), fuW, fuH, fdW, fdH
-        p.px0, p.py0 = int(px0), int(py0)
-        p.sH = int(s.shape[2]) if (readSigns or writeSigns) else 0
-        p.sWbytes = int(s.shape[3]) if (readSigns or writeSigns) else 0
-        p.sx, p.sy, p.swLimit = int(sx), int(sy), int(sw_limit)
-        p.gain, p.slope, p.clamp = float(gain), float(slope), float(clamp)
-        p.flip, p.writeSigns, p.readSigns = int(bool(flip_filters)), int(bool(writeSigns)), int(bool(readSigns))
-        p.fdMirror = int(fd.ndim == 2 and fd.shape[0] > 1 and _mirror_symmetric(fd))
+        signs = readSigns or writeSigns
+        p = filtered_lrelu_params(abi.dtype_code(x.dtype), (N, C, xH, xW), (yH.value, yW.value), abi.strides4(x), abi.strides4(y), int(up), int(down),
+                                  (fuW, fuH), (fdW, fdH), int(px0), int(py0), gain, slope, clamp, flip_filters, write_signs=writeSigns, read_signs=readSigns,
+                                  s_hw=(int(s.shape[2]), int(s.shape[3])) if signs else (0, 0), sx=sx, sy=sy, sw_limit=sw_limit, b_stride=int(b.stride(0)),
+                                  fd_mirror=fd.ndim == 2 and fd.shape[0] > 1 and _mirror_symmetric(fd),
+                                  x=abi.ptr(x), y=abi.ptr(y), b=abi.ptr(b), s=abi.ptr(s) if signs else None, fu=abi.ptr(fu_c), fd=abi.ptr(fd_c))
         partial = partial_max = None
         if return_sum:
             slots = int(lib.sg3_filtered_lrelu_sum_slots(N, C, yH.value, yW.value, int(down)))
@@ -134,9 +159,11 @@ class FilteredLreluPlugin:
         if stream_call_log is not None:
             g = [ctypes.c_int() for _ in range(5)]
             ok = lib.sg3_filtered_lrelu_stream_grid(ctypes.byref(p), *[ctypes.byref(v) for v in g])
+            info = abi.FilteredLreluDispatchInfo()
+            lib.sg3_filtered_lrelu_dispatch(ctypes.byref(p), ctypes.byref(info))
             stream_call_log.append(dict(read=bool(readSigns), write=bool(writeSigns), shape=(N, C, yH.value, yW.value), up=int(up), down=int(down),
                                         planes_per_wave=int(lib.sg3_filtered_lrelu_planes_per_wave(ctypes.byref(p))),
-                                        grid=tuple(v.value for v in g) if ok else None, partial=partial, partial_max=partial_max))
+                                        grid=tuple(v.value for v in g) if ok else None, partial=partial, partial_max=partial_max, plan=info.as_dict()))
         with torch.cuda.device(x.device):
             rc = lib.sg3_filtered_lrelu(ctypes.byref(p), abi.stream_ptr(x.device))
         if abi.check(rc, 'sg3_filtered_lrelu', allow_no_kernel=True) == abi.SG3_NO_KERNEL:

@@ -17,6 +17,7 @@ SG3_OK, SG3_NO_KERNEL, SG3_BAD_ARG, SG3_HIP_ERROR = 0, -1, -2, -3
 SG3_F32, SG3_F16, SG3_F64 = 0, 1, 2
 SG3_CONV_FP32, SG3_CONV_F16X3, SG3_CONV_F16, SG3_CONV_F16X3_F23, SG3_CONV_F16_F23 = 0, 1, 2, 3, 4
 SG3_MODCONV_FP32_MFMA, SG3_MODCONV_TORGB, SG3_MODCONV_ROWS, SG3_MODCONV_FLAT, SG3_MODCONV_GEMM1, SG3_MODCONV_F23 = range(6)   # sg3_modconv_dispatch_info.family
+SG3_FLRELU_NONE, SG3_FLRELU_POINTWISE, SG3_FLRELU_STREAM = range(3)                             # sg3_filtered_lrelu_dispatch_info.kind
 SG3_CONV2D_FORM_F16X3 = 16          # sg3_conv2d_form: first f16x3 form (include/sg3_ops.h)
 _DTYPE = {torch.float32: SG3_F32, torch.float16: SG3_F16, torch.float64: SG3_F64}
 
@@ -31,6 +32,18 @@ class FilteredLreluParams(ctypes.Structure):
                 ('px0', c_i32), ('py0', c_i32), ('sH', c_i32), ('sWbytes', c_i32), ('sx', c_i32), ('sy', c_i32),
                 ('swLimit', c_i32), ('gain', c_f32), ('slope', c_f32), ('clamp', c_f32),
                 ('flip', c_i32), ('writeSigns', c_i32), ('readSigns', c_i32), ('ySumPartial', c_vp), ('fdMirror', c_i32), ('yAbsMaxPartial', c_vp)]
+
+
+class FilteredLreluDispatchInfo(ctypes.Structure):
+    PER_LAUNCH = ('U', 'D', 'VPH', 'RADIAL', 'SIGNS', 'G', 'WIDE', 'nStrips', 'TW', 'ox0Base', 'wideBlocks', 'totalBlocks')
+    _fields_ = ([(n, c_i32) for n in ('kind', 'launches', 'planesPerWave', 'nChunks', 'chunkRows', 'sumSlots', 'fastAct')] +
+                [(n, c_i32 * 2) for n in PER_LAUNCH])
+
+    def as_dict(self):
+        """the call-wide fields, and `launch`: one dict of PER_LAUNCH per launch"""
+        d = {n: getattr(self, n) for n, t in self._fields_ if t is c_i32}
+        d['launch'] = [{n: getattr(self, n)[i] for n in self.PER_LAUNCH} for i in range(self.launches)]
+        return d
 
 
 class FilteredLreluActParams(ctypes.Structure):
@@ -227,6 +240,7 @@ EXPORTS = [
     ('sg3_device_count', ctypes.c_int, []),
     ('sg3_filtered_lrelu', ctypes.c_int, [ctypes.POINTER(FilteredLreluParams), c_vp]),
     ('sg3_filtered_lrelu_planes_per_wave', ctypes.c_int, [ctypes.POINTER(FilteredLreluParams)]),
+    ('sg3_filtered_lrelu_dispatch', ctypes.c_int, [ctypes.POINTER(FilteredLreluParams), ctypes.POINTER(FilteredLreluDispatchInfo)]),
     ('sg3_filtered_lrelu_force_up4_wide', ctypes.c_int, [ctypes.c_int]),
     ('sg3_filtered_lrelu_stream_grid', ctypes.c_int, [ctypes.POINTER(FilteredLreluParams)] + [ctypes.POINTER(ctypes.c_int)] * 5),
     ('sg3_filtered_lrelu_fast_threshold', ctypes.c_float, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float]),

@@ -1,7 +1,8 @@
 // modconv_dispatch_recorder.h -- force-included (-include) in front of csrc/sg3_modconv.hip and csrc/sg3_modconv_f23.hip to
 // record what their host side WOULD launch, without a GPU: the launch macro, the dynamic-LDS attribute call and the device
 // queries are replaced after <hip/hip_runtime.h> has declared the real ones.  Used once per change of the dispatch to regenerate
-// tests/golden/modconv_dispatch.json (see make_modconv_dispatch.py); never part of the product library.
+// tests/golden/modconv_dispatch.json (see make_modconv_dispatch.py); never part of the product library.  csrc/sg3_filtered_lrelu.hip
+// is recorded the same way for tests/golden/flrelu_dispatch.json (make_flrelu_dispatch.py, flrelu_dispatch_recorder.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cxxabi.h>
@@ -32,6 +33,13 @@ inline std::string kernel_name(const void* f) {
 template <class P> auto geometry(const P& p, int) -> decltype((void)p.xTiles, std::string()) {
     char b[160];
     snprintf(b, sizeof b, ",\"nch\":%d,\"xTiles\":%d,\"yTiles\":%d,\"mTiles\":%d,\"outPitch\":%d", p.nch, p.xTiles, p.yTiles, p.mTiles, p.outPitch);
+    return b;
+}
+// work decomposition of the parameter block the filtered_lrelu streaming kernel takes (StreamParams)
+template <class P> auto geometry(const P& p, int) -> decltype((void)p.wideBlocks, std::string()) {
+    char b[200];
+    snprintf(b, sizeof b, ",\"nStrips\":%d,\"TW\":%d,\"ox0Base\":%d,\"wideBlocks\":%d,\"nChunks\":%d,\"CH\":%d,\"totalBlocks\":%d,\"fastAct\":%d",
+             p.nStrips, p.TW, p.ox0Base, p.wideBlocks, p.nChunks, p.CH, p.totalBlocks, p.fastAct);
     return b;
 }
 template <class P> std::string geometry(const P&, long) { return ""; }

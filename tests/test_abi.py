@@ -38,7 +38,7 @@ def test_struct_layout_matches_header():
     for cname, cls in (('sg3_filtered_lrelu_params', _sg3abi.FilteredLreluParams), ('sg3_filtered_lrelu_act_params', _sg3abi.FilteredLreluActParams),
                        ('sg3_upfirdn2d_params', _sg3abi.Upfirdn2dParams), ('sg3_bias_act_params', _sg3abi.BiasActParams),
                        ('sg3_modconv_params', _sg3abi.ModconvParams), ('sg3_modconv_prep_params', _sg3abi.ModconvPrepParams),
-                       ('sg3_modconv_dispatch_info', _sg3abi.ModconvDispatchInfo),
+                       ('sg3_modconv_dispatch_info', _sg3abi.ModconvDispatchInfo), ('sg3_filtered_lrelu_dispatch_info', _sg3abi.FilteredLreluDispatchInfo),
                        ('sg3_conv2d_params', _sg3abi.Conv2dParams), ('sg3_wgrad_params', _sg3abi.WgradParams),
                        ('sg3_fourier_params', _sg3abi.FourierParams), ('sg3_se_params', _sg3abi.SeParams), ('sg3_unfold_params', _sg3abi.UnfoldParams),
                        ('sg3_head_gemm_params', _sg3abi.HeadGemmParams)):
@@ -103,18 +103,11 @@ def _stream_grid(n, c, x, up, down, fu, fd, pad, read=False, write=False):
     lib = _sg3abi.load()
     out = [ctypes.c_int() for _ in range(5)]
     assert lib.sg3_filtered_lrelu_shape(x, x, up, down, fu, 0, fd, 0, pad[0], pad[1], pad[0], pad[1], *[ctypes.byref(o) for o in out]) == 0
-    p = _sg3abi.FilteredLreluParams()
-    p.dtype = _sg3abi.SG3_F32
-    p.N, p.C, p.xH, p.xW, p.yH, p.yW = n, c, x, x, out[0].value, out[1].value
-    for i, v in enumerate((c * x * x, x * x, x, 1)):
-        p.xStride[i] = v
-    for i, v in enumerate((c * p.yH * p.yW, p.yH * p.yW, p.yW, 1)):
-        p.yStride[i] = v
-    p.up, p.down, p.fuW, p.fdW, p.px0, p.py0 = up, down, fu, fd, pad[0], pad[0]
-    p.gain, p.slope, p.clamp = 1.4142135, 0.2, 256.0
-    p.readSigns, p.writeSigns = int(read), int(write)
-    if read or write:
-        p.s, p.sH, p.sWbytes = 16, out[2].value, out[3].value            # a non-null placeholder: the query follows no pointer
+    from torch_utils._hip_plugins import dense_strides, filtered_lrelu_params
+    yh, yw = out[0].value, out[1].value
+    p = filtered_lrelu_params(_sg3abi.SG3_F32, (n, c, x, x), (yh, yw), dense_strides(n, c, x, x), dense_strides(n, c, yh, yw), up, down, (fu, 0), (fd, 0),
+                              pad[0], pad[0], 1.4142135, 0.2, 256.0, False, write_signs=write, read_signs=read, s_hw=(out[2].value, out[3].value),
+                              fu=None, fd=None, x=None, y=None, b=None)         # placeholders: the query follows no pointer
     g = [ctypes.c_int() for _ in range(5)]
     ok = lib.sg3_filtered_lrelu_stream_grid(ctypes.byref(p), *[ctypes.byref(v) for v in g])
     return (ok, p.yH) + tuple(v.value for v in g)

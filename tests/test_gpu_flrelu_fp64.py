@@ -194,19 +194,11 @@ def _grid(n, c, x_hw, fu, fd, up, down, pads, read=False, write=False):
     fdw, fdh = int(fd.shape[-1]), (int(fd.shape[0]) if fd.ndim == 2 else 0)
     out = [ctypes.c_int() for _ in range(5)]
     abi.check(lib.sg3_filtered_lrelu_shape(x_hw[0], x_hw[1], up, down, fuw, fuh, fdw, fdh, *pads, *[ctypes.byref(o) for o in out]), 'sg3_filtered_lrelu_shape')
-    p = abi.FilteredLreluParams()
-    p.dtype = abi.SG3_F32
-    p.N, p.C, p.xH, p.xW, p.yH, p.yW = n, c, x_hw[0], x_hw[1], out[0].value, out[1].value
-    for i, v in enumerate((c * x_hw[0] * x_hw[1], x_hw[0] * x_hw[1], x_hw[1], 1)):
-        p.xStride[i] = v
-    for i, v in enumerate((c * p.yH * p.yW, p.yH * p.yW, p.yW, 1)):
-        p.yStride[i] = v
-    p.fu, p.fd = abi.ptr(fu), abi.ptr(fd)
-    p.up, p.down, p.fuW, p.fuH, p.fdW, p.fdH, p.px0, p.py0 = up, down, fuw, fuh, fdw, fdh, pads[0], pads[2]
-    p.gain, p.slope, p.clamp = 1.0, 0.2, 256.0
-    p.readSigns, p.writeSigns = int(read), int(write)
-    if read or write:
-        p.s, p.sH, p.sWbytes = 16, 1, 1                                 # non-null placeholders
+    from torch_utils._hip_plugins import dense_strides, filtered_lrelu_params
+    yh, yw = out[0].value, out[1].value
+    p = filtered_lrelu_params(abi.SG3_F32, (n, c, x_hw[0], x_hw[1]), (yh, yw), dense_strides(n, c, x_hw[0], x_hw[1]), dense_strides(n, c, yh, yw), up, down,
+                              (fuw, fuh), (fdw, fdh), pads[0], pads[2], 1.0, 0.2, 256.0, False, write_signs=write, read_signs=read, s_hw=(1, 1),
+                              fu=abi.ptr(fu), fd=abi.ptr(fd), x=None, y=None, b=None)         # non-null placeholder for the signs
     g = [ctypes.c_int() for _ in range(5)]
     assert lib.sg3_filtered_lrelu_stream_grid(ctypes.byref(p), *[ctypes.byref(v) for v in g]) == 1
     return tuple(v.value for v in g), (p.yH, p.yW)
