@@ -1102,6 +1102,90 @@ typedef struct sg3_se_bwd_params {
 
 SG3_API int sg3_se_residual_bwd(const sg3_se_bwd_params* p, void* stream);
 
+/* ----------------------------------------------------------------------
+ * LPIPS (AlexNet) criterion (reference criteria/lpips): the pieces besides sg3_conv2d / sg3_conv2d_dgrad.  All float32, exact fp32
+ * arithmetic, no float atomics: every result is bit-identical on repeat.  Tensors are contiguous unless strides are given.
+ *
+ * sg3_lpips_prepare: x [N][3][H][W] (element strides) -> canvas [N][48][OH+2][OW+2], OH = (H - 7) / 4 + 1 (OW likewise):
+ *     canvas[n][c*16 + ry*4 + rx][py][px] = (x[n][c][4 py + ry - 2][4 px + rx - 2] - mean[c]) / std[c]   inside the image, else 0
+ * Over it the 11x11 stride-4 pad-2 convolution is a VALID 3x3 stride-1 convolution of 48 channels whose weight is the 11x11 one
+ * zero-extended to 12x12 and regrouped [O][3][3][4][3][4] -> [O][48][3][3].
+ * sg3_lpips_prepare_bwd: the adjoint; x is then the OUTPUT (dx = dcanvas / std, times scale[0] when scale != NULL; exactly 0 for
+ * image rows / columns beyond the canvas, which the convolution never reads) and canvas the INPUT.
+ * ---------------------------------------------------------------------- */
+typedef struct sg3_lpips_prepare_params {
+    float*         x;              /* [N][3][H][W]: read (forward) or written (adjoint) */
+    int64_t        xStride[4];
+    float*         canvas;         /* [N][48][OH+2][OW+2]: written (forward) or read (adjoint) */
+    const float*   scale;          /* adjoint only: device scalar multiplied into dx, or NULL */
+    int32_t        N, H, W;
+    float          mean[3];
+    float          std[3];
+} sg3_lpips_prepare_params;
+
+SG3_API int sg3_lpips_prepare(const sg3_lpips_prepare_params* p, void* stream);
+SG3_API int sg3_lpips_prepare_bwd(const sg3_lpips_prepare_params* p, void* stream);
+
+/* 5x5 stride-1 pad-2 convolution on the fp32 matrix cores (v_mfma_f32_32x32x2_f32): out = conv(x, w) (+ bias) (ReLU when relu != 0).
+ * wPacked: sg3_conv2d_k5_pack of w [O][I][5][5] into [O][ceil(I/8)][25][8] (sg3_conv2d_k5_packed_floats floats).  The data gradient
+ * of such a convolution is the same call on the transposed, spatially flipped weight wT[i][o][4-ky][4-kx]. */
+typedef struct sg3_conv2d_k5_params {
+    const float*   x;              /* [N][I][H][W] */
+    const float*   wPacked;
+    const float*   bias;           /* [O] or NULL */
+    float*         out;            /* [N][O][H][W] */
+    int32_t        N, I, O, H, W;
+    int32_t        relu;
+} sg3_conv2d_k5_params;
+
+SG3_API int64_t sg3_conv2d_k5_packed_floats(int O, int I);
+SG3_API int sg3_conv2d_k5_pack(const float* w, float* wPacked, int O, int I, void* stream);
+SG3_API int sg3_conv2d_k5(const sg3_conv2d_k5_params* p, void* stream);
+
+/* MaxPool2d(kernel 3, stride 2, no padding, floor): y [N][C][(H-3)/2+1][(W-3)/2+1], values bit-equal to the library's. */
+typedef struct sg3_maxpool3s2_params {
+    const float*   x;              /* [N][C][H][W] */
+    float*         y;
+    int32_t        N, C, H, W;
+} sg3_maxpool3s2_params;
+
+SG3_API int sg3_maxpool3s2(const sg3_maxpool3s2_params* p, void* stream);
+
+/* Its backward in gather form: dx[pixel] = sum of dy over the (<= 4) windows whose first maximum in row-major order is that pixel,
+ * + addend[pixel] (addend != NULL, contiguous like x), then times (x > 0) when reluMask != 0.  Pixels no window covers receive
+ * only the addend.  dx is written through element strides (it may be the interior of a larger zeroed buffer). */
+typedef struct sg3_maxpool3s2_bwd_params {
+    const float*   x;              /* [N][C][H][W]: the forward's input */
+    const float*   dy;             /* [N][C][OH][OW] */
+    const float*   addend;         /* [N][C][H][W] or NULL */
+    float*         dx;             /* [N][C][H][W] through dxStride */
+    int64_t        dxStride[4];
+    int32_t        N, C, H, W;
+    int32_t        reluMask;
+} sg3_maxpool3s2_bwd_params;
+
+SG3_API int sg3_maxpool3s2_bwd(const sg3_maxpool3s2_bwd_params* p, void* stream);
+
+/* One LPIPS layer:  value[n] = sum_hw sum_c lin[c] (a_c - b_c)^2 / (h w),  a = fx / (|fx| + 1e-10), b = fy / (|fy| + 1e-10), the
+ * norms over channels per pixel.  dfx != NULL also receives d value[n] / d fx[n] in closed form:
+ *     g_c = 2 lin[c] (a_c - b_c) / (h w),   dfx_c = g_c / (r + eps) - fx_c (sum_j g_j fx_j) / (r (r + eps)^2),   r = |fx|
+ * and exactly 0 for every channel of a pixel with r = 0; with reluMask != 0 it is 0 wherever fx <= 0 as well.
+ * partial: scratch of N * sg3_lpips_head_blocks(h, w) floats.  counter: N int32 that are ZERO on entry and are left zero. */
+typedef struct sg3_lpips_head_params {
+    const float*   fx;             /* [N][C][h][w] */
+    const float*   fy;             /* [N][C][h][w] */
+    const float*   lin;            /* [C] */
+    float*         value;          /* [N] */
+    float*         dfx;            /* [N][C][h][w] or NULL */
+    float*         partial;
+    int32_t*       counter;
+    int32_t        N, C, h, w;
+    int32_t        reluMask;
+} sg3_lpips_head_params;
+
+SG3_API int sg3_lpips_head_blocks(int h, int w);
+SG3_API int sg3_lpips_head(const sg3_lpips_head_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,9 +5,10 @@ Adam so that synthesis(latent) reproduces the target:  loss = l2_lambda * MSE + 
 the fp32 synthesis path on the HIP kernels; the backward runs through the ops' autograd functions (filtered_lrelu:
 sign-tensor adjoint; modulated conv: gradients of the reference formulation).
 
-LPIPS needs pretrained AlexNet weights that are not part of this package: pass `lpips_loss` (a callable
-(generated, real) -> scalar tensor) or set opts.lpips_lambda = 0.  Image decoding / the side-by-side JPEG dumps of the
-reference are I/O outside the hot path: targets are tensors in [-1, 1].
+LPIPS is criteria/lpips (AlexNet, HIP forward and backward); its pretrained weights are not part of this package.  Either pass
+`lpips_loss` (an `LPIPS(...)` instance or any callable (generated, real) -> scalar tensor), or set `opts.lpips_alexnet_weights`
+and `opts.lpips_lin_weights` (state dicts or paths) and the criterion is built from them, or set opts.lpips_lambda = 0.  Image
+decoding / the side-by-side JPEG dumps of the reference are I/O outside the hot path: targets are tensors in [-1, 1].
 """
 import types
 
@@ -59,9 +60,14 @@ class PTI:
         self.opts = opts
         self.device = opts.device
         self.mse_loss = nn.MSELoss().to(self.device).eval()
+        alex, lin = getattr(opts, 'lpips_alexnet_weights', None), getattr(opts, 'lpips_lin_weights', None)
+        if lpips_loss is None and opts.lpips_lambda > 0 and alex is not None and lin is not None:
+            from criteria.lpips import LPIPS
+            lpips_loss = LPIPS(net_type='alex', alexnet_weights=alex, lin_weights=lin).to(self.device)
         self.lpips_loss = lpips_loss
         if opts.lpips_lambda > 0 and lpips_loss is None:
-            raise RuntimeError('PTI: opts.lpips_lambda > 0 needs an lpips_loss callable (the pretrained LPIPS network is external)')
+            raise RuntimeError('PTI: opts.lpips_lambda > 0 needs an lpips_loss callable, or the weights of criteria.lpips.LPIPS as '
+                               'opts.lpips_alexnet_weights and opts.lpips_lin_weights (the pretrained weights are not part of this package)')
         self.history = []                                 # (step, loss, lpips, l2) floats of the last optimize_model call
 
     @staticmethod

@@ -6,6 +6,9 @@ a contiguous slice of each mini-batch; the per-rank losses are weighted so that 
 mean, and the gradients are summed with ONE all-reduce per step over a single flat bucket that all parameter
 gradients alias (21 M parameters = 84 MB fp32 for T-1024; no per-tensor collectives, no copy in or out).  The
 optimizer step is replicated, so the replicas stay bit-identical without broadcasting weights.
+
+The LPIPS term is `criteria.lpips.LPIPS`, passed as `lpips_loss` or built by `PTI.__init__` from `opts.lpips_alexnet_weights` and
+`opts.lpips_lin_weights`; every rank holds its own frozen copy.
 """
 import numpy as np
 import torch

@@ -233,6 +233,30 @@ class SeBwdParams(ctypes.Structure):
                 ('N', c_i32), ('C', c_i32), ('H', c_i32), ('W', c_i32), ('R', c_i32), ('inH', c_i32), ('inW', c_i32)]
 
 
+class LpipsPrepareParams(ctypes.Structure):
+    _fields_ = [('x', c_vp), ('xStride', c_i64 * 4), ('canvas', c_vp), ('scale', c_vp), ('N', c_i32), ('H', c_i32), ('W', c_i32),
+                ('mean', c_f32 * 3), ('std', c_f32 * 3)]
+
+
+class Conv2dK5Params(ctypes.Structure):
+    _fields_ = [('x', c_vp), ('wPacked', c_vp), ('bias', c_vp), ('out', c_vp),
+                ('N', c_i32), ('I', c_i32), ('O', c_i32), ('H', c_i32), ('W', c_i32), ('relu', c_i32)]
+
+
+class Maxpool3s2Params(ctypes.Structure):
+    _fields_ = [('x', c_vp), ('y', c_vp), ('N', c_i32), ('C', c_i32), ('H', c_i32), ('W', c_i32)]
+
+
+class Maxpool3s2BwdParams(ctypes.Structure):
+    _fields_ = [('x', c_vp), ('dy', c_vp), ('addend', c_vp), ('dx', c_vp), ('dxStride', c_i64 * 4),
+                ('N', c_i32), ('C', c_i32), ('H', c_i32), ('W', c_i32), ('reluMask', c_i32)]
+
+
+class LpipsHeadParams(ctypes.Structure):
+    _fields_ = [('fx', c_vp), ('fy', c_vp), ('lin', c_vp), ('value', c_vp), ('dfx', c_vp), ('partial', c_vp), ('counter', c_vp),
+                ('N', c_i32), ('C', c_i32), ('h', c_i32), ('w', c_i32), ('reluMask', c_i32)]
+
+
 # every symbol include/sg3_ops.h declares: (name, restype, argtypes)
 EXPORTS = [
     ('sg3_abi_version', ctypes.c_int, []),
@@ -295,6 +319,15 @@ EXPORTS = [
     ('sg3_face_pool', ctypes.c_int, [ctypes.POINTER(FacePoolParams), c_vp]),
     ('sg3_conv2d_dgrad', ctypes.c_int, [ctypes.POINTER(Conv2dDgradParams), c_vp]),
     ('sg3_se_residual_bwd', ctypes.c_int, [ctypes.POINTER(SeBwdParams), c_vp]),
+    ('sg3_lpips_prepare', ctypes.c_int, [ctypes.POINTER(LpipsPrepareParams), c_vp]),
+    ('sg3_lpips_prepare_bwd', ctypes.c_int, [ctypes.POINTER(LpipsPrepareParams), c_vp]),
+    ('sg3_conv2d_k5_packed_floats', ctypes.c_int64, [ctypes.c_int] * 2),
+    ('sg3_conv2d_k5_pack', ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp]),
+    ('sg3_conv2d_k5', ctypes.c_int, [ctypes.POINTER(Conv2dK5Params), c_vp]),
+    ('sg3_maxpool3s2', ctypes.c_int, [ctypes.POINTER(Maxpool3s2Params), c_vp]),
+    ('sg3_maxpool3s2_bwd', ctypes.c_int, [ctypes.POINTER(Maxpool3s2BwdParams), c_vp]),
+    ('sg3_lpips_head_blocks', ctypes.c_int, [ctypes.c_int] * 2),
+    ('sg3_lpips_head', ctypes.c_int, [ctypes.POINTER(LpipsHeadParams), c_vp]),
 ]
 
 _lib = None

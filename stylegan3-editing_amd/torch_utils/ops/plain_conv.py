@@ -46,7 +46,12 @@ def overflowed(device):
 class PackedConv:
     """Weights of one convolution in the implicit-GEMM operand layout, plus its fused epilogue / prologue vectors."""
 
-    def __init__(self, weight, out_scale=None, bias=None, in_scale=None, in_shift=None, act=ACT_NONE, slope=None, stride=1, padding=0):
+    def __init__(self, weight, out_scale=None, bias=None, in_scale=None, in_shift=None, act=ACT_NONE, slope=None, stride=1, padding=0,
+                 precision=None):
+        # `precision`: 'fp32' / 'f16x3' for this object whatever the module-wide `precision` says (the LPIPS criterion runs exact fp32);
+        # None follows the module-wide setting at every call
+        assert precision in (None, 'fp32', 'f16x3')
+        self.precision = precision
         assert weight.is_cuda and weight.dtype == torch.float32 and weight.ndim == 4 and weight.shape[2] == weight.shape[3]
         self.O, self.I, self.k = int(weight.shape[0]), int(weight.shape[1]), int(weight.shape[2])
         assert self.k in (1, 3) and stride in (1, 2)
@@ -80,7 +85,7 @@ class PackedConv:
         return self.run(x)
 
     def _params(self, x, out):
-        split = precision == 'f16x3'
+        split = (self.precision or precision) == 'f16x3'
         prec = abi.SG3_CONV_F16X3 if split else abi.SG3_CONV_FP32
         n, _, h, w = (int(v) for v in x.shape)
         p = abi.Conv2dParams()
@@ -92,7 +97,7 @@ class PackedConv:
         return p
 
     def form(self, x):
-        """The kernel form `run(x)` launches under the current `precision` (sg3_conv2d_form: 0 .. 11 for 'fp32',
+        """The kernel form `run(x)` launches under the current `precision` (or the object's own; sg3_conv2d_form: 0 .. 11 for 'fp32',
         abi.SG3_CONV2D_FORM_F16X3 + 0 .. 5 for 'f16x3'); nothing is launched."""
         assert x.is_cuda and x.ndim == 4 and x.shape[1] == self.I
         with torch.cuda.device(x.device):
