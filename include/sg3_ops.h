@@ -373,6 +373,9 @@ enum {
                           * instructions, the same split arithmetic on the transformed operands (inputs transformed in fp32 before
                           * the split, weights at pack time).  3x3 kernels on fp32 tensors with even W, pad and output row pitch
                           * only (sg3_modconv_f23_supported); its own packed layout, so prep and convolution must agree */
+    SG3_CONV_FP32_CHAINS = 5, /* sg3_conv2d only: SG3_CONV_FP32 on the same packed weights with four accumulation chains per output
+                          * (summed pairwise at the end) instead of one: a quarter of the rounding-error growth along K, for the
+                          * recorded forward of encoder training; 64- and 32-channel tiles */
     SG3_CONV_F16_F23 = 4, /* SG3_CONV_F16 in the same transform domain, for fp16 tensors (the reference's `use_fp16` layers,
                           * networks_stylegan3.py:355-366): transformed inputs and weights rounded to fp16 once, one product per K step,
                           * fp32 accumulation, fp16 output.  Same shape rules; packed layout without lo fragments (half the size) */
@@ -578,6 +581,7 @@ typedef struct sg3_conv2d_params {
 SG3_API int sg3_conv2d(const sg3_conv2d_params* p, void* stream);
 
 /* Diagnostic: the kernel form sg3_conv2d launches for *p (same checks, nothing launched; negative status for invalid params).
+ *   SG3_CONV_FP32_CHAINS:  12 (64 ch x 2 rows) or 13 (32 ch x 4 rows)
  *   SG3_CONV_FP32:  ((k == 3) * 2 + (stride == 2)) * 3 + tile, tile 0 = 128 ch x 4 rows, 1 = 64 ch x 2 rows, 2 = 32 ch x 4 rows
  *                   (12 forms);
  *   SG3_CONV_F16X3: SG3_CONV2D_FORM_F16X3 + 0 (1x1 stride 2), 1 (1x1 stride 1), 2 (3x3 stride 2), 3 (3x3 stride 1, outH <= 16,
@@ -1185,6 +1189,105 @@ typedef struct sg3_lpips_head_params {
 
 SG3_API int sg3_lpips_head_blocks(int h, int w);
 SG3_API int sg3_lpips_head(const sg3_lpips_head_params* p, void* stream);
+
+/* ----------------------------------------------------------------------
+ * Training the encoder trunk: weight gradient of sg3_conv2d's convolutions summed over the batch, exact fp32 matrix products:
+ *     dw[o][i][ky][kx] = sum_{n,oy,ox} dy[n][o][oy][ox] xt[n][i][oy stride + ky - k / 2][ox stride + kx - k / 2]
+ *     xt = inScale[i] x + inShift[i] on real pixels (both NULL: xt = x), 0 in the padding; k in {1, 3}, stride in {1, 2}.
+ * The K dimension is cut into chunks: chunk c = (n OH + oy) xSegs + xs is the output pixels [P xs, min(OW, P xs + P)) of row oy of
+ * sample n, P = 32 / stride.  Split j of nSplit sums the chunks [j chunksPerSplit, min((j + 1) chunksPerSplit, N OH xSegs)) into its own partial, and a
+ * second launch adds the partials in split order (one split: written to dw directly).  sg3_conv2d_wgrad_sum_splits is host only and does
+ * not depend on the device.  partial: nSplit O I k k floats of scratch (may be NULL for one split).  All tensors contiguous float32.
+ * ---------------------------------------------------------------------- */
+typedef struct sg3_conv2d_wgrad_sum_params {
+    const float*   x;              /* [N][I][H][W] */
+    const float*   dy;             /* [N][O][OH][OW] */
+    const float*   inScale;        /* [I] or NULL */
+    const float*   inShift;        /* [I] or NULL */
+    float*         dw;             /* [O][I][k][k] */
+    float*         partial;
+    int32_t        N, I, O, H, W;
+    int32_t        k, stride;
+} sg3_conv2d_wgrad_sum_params;
+
+SG3_API int sg3_conv2d_wgrad_sum_splits(int N, int I, int O, int H, int W, int k, int stride, int* nSplit, int* chunksPerSplit, int* xSegs);
+SG3_API int sg3_conv2d_wgrad_sum(const sg3_conv2d_wgrad_sum_params* p, void* stream);
+
+/* ----------------------------------------------------------------------
+ * Training-mode BatchNorm2d (csrc/sg3_bn_train.hip).  Contiguous float32 [N][C][H][W]; per-channel vectors [C]; float64 sums in a
+ * fixed order.  `partial` is scratch of 2 C sg3_bn_train_partials(N, H, W) doubles.
+ *   stats:       mean (+ meanLo), var (biased), invstd = 1 / sqrt(var + eps), a = gamma invstd, b = beta - mean a   (gamma / beta NULL: 1 / 0)
+ *   apply:       v = scale[c] (x - centre[c] - centreLo[c]) + shift[c] (NULL: 0);  pre = v (pre != NULL);  y = v > 0 ? v : v slope[c] (slope != NULL)
+ *   bwd_reduce:  sum1[c] = sum dy,  sum2[c] = sum dy t;  mode 0: t = (x - mean[c] - meanLo[c]) invstd[c];  mode 1: t = min(x, 0), sum1 may be NULL,
+ *                and masked = dy (x > 0 ? 1 : slope[c]) when asked
+ *   bwd_apply:   v = scale[c] (dy - sum1[c] / M - xhat sum2[c] / M),  M = N H W;  v += addend (element strides);  raw = v (raw != NULL);
+ *                dx = v (act > 0 ? 1 : slope[c])  (act != NULL: contiguous like dx)
+ * ---------------------------------------------------------------------- */
+typedef struct sg3_bn_train_stats_params {
+    const float*   x;
+    const float*   gamma;
+    const float*   beta;
+    double*        partial;
+    float*         mean;
+    float*         meanLo;         /* mean - (float)mean: the part of the float64 mean one float does not hold */
+    float*         var;
+    float*         invstd;
+    float*         a;
+    float*         b;
+    int32_t        N, C, H, W;
+    float          eps;
+} sg3_bn_train_stats_params;
+
+typedef struct sg3_bn_train_apply_params {
+    const float*   x;
+    const float*   scale;
+    const float*   shift;
+    const float*   centre;
+    const float*   centreLo;       /* or NULL */
+    const float*   slope;
+    float*         y;
+    float*         pre;
+    int32_t        N, C, H, W;
+} sg3_bn_train_apply_params;
+
+typedef struct sg3_bn_train_bwd_reduce_params {
+    const float*   dy;
+    const float*   x;
+    const float*   mean;
+    const float*   meanLo;         /* or NULL */
+    const float*   invstd;
+    const float*   slope;          /* [C], with masked */
+    float*         masked;         /* mode 1, or NULL: dy (x > 0 ? 1 : slope[c]) */
+    double*        partial;
+    float*         sum1;
+    float*         sum2;
+    int32_t        N, C, H, W;
+    int32_t        mode;
+} sg3_bn_train_bwd_reduce_params;
+
+typedef struct sg3_bn_train_bwd_apply_params {
+    const float*   dy;
+    const float*   x;
+    const float*   mean;
+    const float*   meanLo;         /* or NULL */
+    const float*   invstd;
+    const float*   scale;
+    const float*   sum1;
+    const float*   sum2;
+    const float*   addend;
+    int64_t        addStride[4];
+    const float*   act;
+    const float*   slope;
+    float*         dx;
+    float*         raw;
+    int32_t        N, C, H, W;
+} sg3_bn_train_bwd_apply_params;
+
+SG3_API int sg3_bn_train_partials(int N, int H, int W);
+SG3_API int sg3_bn_train_stats(const sg3_bn_train_stats_params* p, void* stream);
+SG3_API int sg3_bn_train_apply(const sg3_bn_train_apply_params* p, void* stream);
+SG3_API int sg3_bn_train_bwd_reduce(const sg3_bn_train_bwd_reduce_params* p, void* stream);
+SG3_API int sg3_bn_train_bwd_apply(const sg3_bn_train_bwd_apply_params* p, void* stream);
 
 #ifdef __cplusplus
 }

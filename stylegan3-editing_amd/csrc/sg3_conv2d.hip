@@ -20,7 +20,10 @@ struct PlainConvParams {
     int nch, xTiles, yTiles, mTiles, totalBlocks;
 };
 
-template <int KS, int STRIDE, int WM, int WN, int TM, int TN>
+// CHAINS = 4 (SG3_CONV_FP32_CHAINS, the recorded training forward): one accumulator per k lane pair of the fragment, summed in the
+// epilogue, as conv2d_dgrad_kernel does -- a single accumulator is one chain of taps x I / 2 dependent additions whose rounding error
+// grows with its length (measured on the 24-unit trunk: 1.5 .. 2.5 x the error of a library convolution; four chains: level with it).
+template <int KS, int STRIDE, int WM, int WN, int TM, int TN, int CHAINS = 1>
 __global__ void __launch_bounds__(256)
 conv2d_mfma_kernel(PlainConvParams p) {
     constexpr int TAPS = ConvK<KS>::TAPS, KC = ConvK<KS>::KC;
@@ -51,13 +54,16 @@ conv2d_mfma_kernel(PlainConvParams p) {
     const int o0 = mt * BM, x0 = xt * 32, y0 = yt * ROWS;
     const float* xin = p.x + (size_t)n * p.I * p.H * p.W;
 
-    f32x16 acc[TM][TN];
+    static_assert(CHAINS == 1 || CHAINS == 4, "one accumulator, or one per k lane pair");
+    f32x16 acc[CHAINS][TM][TN];
+#pragma unroll
+    for (int c = 0; c < CHAINS; c++)
 #pragma unroll
     for (int a = 0; a < TM; a++)
 #pragma unroll
         for (int b = 0; b < TN; b++)
 #pragma unroll
-            for (int r = 0; r < 16; r++) acc[a][b][r] = 0.f;
+            for (int r = 0; r < 16; r++) acc[c][a][b][r] = 0.f;
 
     f32x4 ra[A_PER];
     float rb[B_PER];
@@ -132,7 +138,7 @@ conv2d_mfma_kernel(PlainConvParams p) {
                     for (int a = 0; a < TM; a++)
 #pragma unroll
                         for (int b = 0; b < TN; b++)
-                            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[a][q], fb[b][q], acc[a][b], 0, 0, 0);
+                            acc[q % CHAINS][a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[a][q], fb[b][q], acc[q % CHAINS][a][b], 0, 0, 0);
             }
         }
     }
@@ -151,7 +157,7 @@ conv2d_mfma_kernel(PlainConvParams p) {
             for (int b = 0; b < TN; b++) {
                 const int gy = y0 + wn * TN + b;
                 if (gy < p.outH && gx < p.outW) {
-                    float v = acc[a][b][r] + bv;
+                    float v = (CHAINS == 4 ? (acc[0][a][b][r] + acc[1 % CHAINS][a][b][r]) + (acc[2 % CHAINS][a][b][r] + acc[3 % CHAINS][a][b][r]) : acc[0][a][b][r]) + bv;
                     if (p.act) v = v < 0.f ? v * sl : v;
                     outp[((size_t)o * p.outH + gy) * p.outW + gx] = v;
                 }
@@ -511,12 +517,12 @@ static int dispatch_plain_f16x3(const sg3_conv2d_params& q, hipStream_t st) {
     }
 }
 
-template <int KS, int STRIDE, int WM, int WN, int TM, int TN>
+template <int KS, int STRIDE, int WM, int WN, int TM, int TN, int CHAINS = 1>
 static int launch_plain(const sg3_conv2d_params& q, hipStream_t st) {
     PlainConvParams p;
     const int rc = plain_params(q, WM * TM * 32, WN * TN, ConvK<KS>::KC, p);
     if (rc != SG3_OK) return rc;
-    hipLaunchKernelGGL((conv2d_mfma_kernel<KS, STRIDE, WM, WN, TM, TN>), dim3((unsigned)p.totalBlocks), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((conv2d_mfma_kernel<KS, STRIDE, WM, WN, TM, TN, CHAINS>), dim3((unsigned)p.totalBlocks), dim3(256), 0, st, p);
     SG3_LAUNCH_CHECK("conv2d_mfma_kernel");
     return SG3_OK;
 }
@@ -532,6 +538,8 @@ static int plain_tile(const sg3_conv2d_params& q) {
 
 template <int KS, int STRIDE>
 static int dispatch_plain(const sg3_conv2d_params& q, hipStream_t st) {
+    if (q.precision == SG3_CONV_FP32_CHAINS)             // four accumulators per tile: the 64- and 32-channel tiles only
+        return q.O > 32 ? launch_plain<KS, STRIDE, 2, 2, 1, 1, 4>(q, st) : launch_plain<KS, STRIDE, 1, 4, 1, 1, 4>(q, st);
     switch (plain_tile(q)) {
     case 0: return launch_plain<KS, STRIDE, 2, 2, 2, 2>(q, st);
     case 1: return launch_plain<KS, STRIDE, 2, 2, 1, 1>(q, st);
@@ -575,7 +583,7 @@ static int check_conv2d(const sg3_conv2d_params* p) {
         SG3_REQUIRE((int64_t)p->I * p->H * p->W * 4 < (int64_t)1 << 31, "conv2d: f16x3 needs a sample below 2 GiB (32-bit offsets)");
         return SG3_OK;
     }
-    SG3_REQUIRE(p->precision == SG3_CONV_FP32, "conv2d: bad precision");
+    SG3_REQUIRE(p->precision == SG3_CONV_FP32 || p->precision == SG3_CONV_FP32_CHAINS, "conv2d: bad precision");
     return SG3_OK;
 }
 
@@ -584,6 +592,7 @@ int sg3_conv2d_form(const sg3_conv2d_params* p) {
     const int rc = check_conv2d(p);
     if (rc != SG3_OK) return rc;
     if (p->precision == SG3_CONV_F16X3) return SG3_CONV2D_FORM_F16X3 + plain_f16x3_form(*p);
+    if (p->precision == SG3_CONV_FP32_CHAINS) return 12 + (p->O > 32 ? 0 : 1);
     return ((p->k == 3 ? 2 : 0) + (p->stride == 2 ? 1 : 0)) * 3 + plain_tile(*p);
 }
 

@@ -2,9 +2,11 @@
 with the reference so its checkpoints load (reference models/setgan/encoder/encoders/helpers.py: get_blocks :30-55,
 SEModule :57-73, bottleneck_IR :76-95, bottleneck_IR_SE :98-120).
 
-`forward()` is the plain PyTorch definition (used on CPU and for training); on a GPU in eval mode the owning encoder
+`forward()` is the plain PyTorch definition (used on CPU and, by default, for training); on a GPU in eval mode the owning encoder
 calls `forward_hip()`, which runs the two 3x3 convolutions on the matrix cores with their element-wise neighbours
 fused (torch_utils/ops/plain_conv.py): BN1 as an input affine of conv1, PReLU as its epilogue, BN2 folded into conv2.
+With the encoder's `native_training` switch on, train mode runs `forward_train_record()` / `backward_train()`: batch statistics,
+and gradients for the input and every parameter from libsg3hip.
 """
 import os
 from collections import namedtuple
@@ -83,6 +85,7 @@ class _ResidualUnit(Module):
             layers.append(SEModule(depth, 16))
         self.res_layer = Sequential(*layers)
         self._packed = None
+        self._train_packed = None
 
     def forward(self, x):
         return self.res_layer(x) + self.shortcut_layer(x)
@@ -193,6 +196,114 @@ class _ResidualUnit(Module):
         if post is None:
             return gk['conv1'].run(dh1, (h, w), addend=addend)
         return gk['conv1'].run(dh1, (h, w), addend=addend, act=post[0], slope=post[1])
+
+    # ---- train mode: batch statistics, and gradients for the input and every parameter ----
+    def _train_packs(self):
+        """Forward and transposed weights of the unit's convolutions with nothing folded in (in training the BatchNorms are the batch's),
+        keyed on (data_ptr, _version) of the weights: rebuilt after an optimizer step, kept between the iterations of one step."""
+        convs = [self.res_layer[1], self.res_layer[3]] + ([self.shortcut_layer[0]] if isinstance(self.shortcut_layer, Sequential) else [])
+        key = tuple((c.weight.data_ptr(), c.weight._version) for c in convs)
+        tp = getattr(self, '_train_packed', None)
+        if tp is None or tp['key'] != key:
+            from torch_utils.ops.plain_conv import ACT_NONE, PackedConv
+            from torch_utils.ops.plain_conv_grad import PackedDgrad
+            dev, depth = convs[0].weight.device, int(convs[0].weight.shape[0])
+            tp = dict(key=key, one=torch.ones([depth], device=dev), zero=torch.zeros([depth], device=dev),
+                      conv1=PackedConv(convs[0].weight, act=ACT_NONE, stride=1, padding=1, chains=True), dgrad1=PackedDgrad(convs[0].weight, stride=1),
+                      conv2=PackedConv(convs[1].weight, act=ACT_NONE, stride=self.stride, padding=1, chains=True), dgrad2=PackedDgrad(convs[1].weight, stride=self.stride))
+            if len(convs) == 3:
+                tp['shortcut'] = PackedConv(convs[2].weight, act=ACT_NONE, stride=self.stride, padding=0, chains=True)
+                tp['dshortcut'] = PackedDgrad(convs[2].weight, stride=self.stride)
+            self._train_packed = tp
+        return tp
+
+    def forward_train_record(self, x, stats_out=None):
+        """`forward` in train mode on libsg3hip, keeping what `backward_train` needs -> (out, saved):
+            BN1 statistics; conv1 with the batch's affine fused, raw; PReLU; conv2, raw; BN2 statistics and apply;
+            the shortcut (projection: 1x1 convolution, BatchNorm statistics and apply); the squeeze-and-excitation tail (IR: one add).
+        Seven ABI calls for IR-SE (six for IR), three more with a projection, once the packs exist.  The convolutions follow
+        `plain_conv.precision` ('fp32' takes the four-chain form); the split-precision overflow flag is the CALLER's to reset, read and
+        answer with a repeat under 'fp32' (`BackboneEncoder._trunk_train_forward` does so for the whole trunk: one flag read per
+        forward, not one per unit).  The running statistics are NOT touched: every (BatchNorm2d, Stats) pair is appended to `stats_out`, and the caller applies them once its forward is accepted
+        (torch_utils/ops/batchnorm_train.update_running)."""
+        from torch_utils.ops import batchnorm_train as bt
+        tp = self._train_packs()
+        bn1, _, prelu, _, bn2 = (self.res_layer[i] for i in range(5))
+        x = x.contiguous()
+        st1 = bt.stats(x, bn1.weight, bn1.bias, bn1.eps)
+        pre = tp['conv1'].run(x, in_scale=st1.a, in_shift=st1.b)
+        h1 = bt.apply(pre, tp['one'], tp['zero'], slope=prelu.weight)
+        c2 = tp['conv2'].run(h1)
+        st2 = bt.stats(c2, bn2.weight, bn2.bias, bn2.eps)
+        res = bt.apply(c2, st2.a, bn2.bias, centre=st2.mean, centre_lo=st2.mean_lo)
+        pairs = [(bn1, st1), (bn2, st2)]
+        sc_raw = st_s = None
+        if 'shortcut' in tp:
+            sbn = self.shortcut_layer[1]
+            sc_raw = tp['shortcut'].run(x)
+            st_s = bt.stats(sc_raw, sbn.weight, sbn.bias, sbn.eps)
+            shortcut = bt.apply(sc_raw, st_s.a, sbn.bias, centre=st_s.mean, centre_lo=st_s.mean_lo)
+            pairs.append((sbn, st_s))
+        else:
+            shortcut = x if self.stride == 1 else x[:, :, ::self.stride, ::self.stride]
+        mean = None
+        if self.use_se:
+            from torch_utils.ops import se_ops
+            se = self.res_layer[5]
+            out, mean = se_ops.se_residual_record(res, shortcut, se.fc1.weight, se.fc2.weight)
+        else:
+            out = res + shortcut
+        if stats_out is not None:
+            stats_out.extend(pairs)
+        return out, (x, st1, pre, h1, c2, st2, res, mean, sc_raw, st_s, prelu.weight.detach().to(torch.float32).contiguous(), tp)
+
+    def backward_train(self, saved, dout, post=None):
+        """Gradient of `forward_train_record` -> (dx, grads), grads keyed like `named_parameters()`:
+            the squeeze-and-excitation backward (its dg and the saved mean give dfc1 / dfc2 as small matrix products); BN2 backward
+            (sums, then the pass); wgrad2; dgrad2; the slope gradient, whose launch also applies the PReLU derivative (from the saved
+            PRE-activation: a slope may be zero); wgrad1 with the BN1 affine fused; dgrad1; BN1 backward with the shortcut path's
+            gradient as the addend; with a projection its BatchNorm backward, wgrad and dgrad.
+        `post` = (act, slope): dx is multiplied by the derivative of a PReLU in front of the unit (the stem's) and returned as
+        (dx, dx before that mask).  Ten ABI calls for IR-SE (nine for IR), four more with a projection; not counted: the torch
+        operations of `se_ops.se_weight_grads` (the gate recomputed from the saved mean, then the two matrix products) and, for IR with a
+        stride-2 identity shortcut, torch's zero-fill and strided copy.  dbeta / dgamma of one BatchNorm are two rows of one [2,C]
+        tensor: independent values, one storage (autograd copies them into `.grad`; clone before editing one in place)."""
+        from torch_utils.ops import batchnorm_train as bt
+        from torch_utils.ops.plain_conv_wgrad import wgrad
+        x, st1, pre, h1, c2, st2, res, mean, sc_raw, st_s, slope, tp = saved
+        h, w = int(x.shape[2]), int(x.shape[3])
+        identity_s2 = 'shortcut' not in tp and self.stride != 1
+        dout = dout.contiguous()
+        g = {}
+        dsc = None
+        if self.use_se:
+            from torch_utils.ops import se_ops
+            se = self.res_layer[5]
+            dres, dsc, dg = se_ops.se_residual_bwd_train(dout, res, mean, se.fc1.weight, se.fc2.weight, scatter_hw=(h, w) if identity_s2 else None)
+            g['res_layer.5.fc1.weight'], g['res_layer.5.fc2.weight'] = se_ops.se_weight_grads(dg, mean, se.fc1.weight, se.fc2.weight)
+        else:
+            dres = dout
+            if identity_s2:
+                dsc = dout.new_zeros([dout.shape[0], dout.shape[1], h, w])
+                dsc[:, :, ::self.stride, ::self.stride] = dout
+        g['res_layer.4.bias'], g['res_layer.4.weight'] = bt.backward_reduce(dres, c2, st2)
+        dc2 = bt.backward_apply(dres, c2, st2, g['res_layer.4.bias'], g['res_layer.4.weight'])
+        g['res_layer.3.weight'] = wgrad(h1, dc2, 3, self.stride)
+        dh1 = tp['dgrad2'].run(dc2, (h, w))
+        g['res_layer.2.weight'], dpre = bt.slope_grad(dh1, pre, slope)
+        g['res_layer.1.weight'] = wgrad(x, dpre, 3, 1, in_scale=st1.a, in_shift=st1.b)
+        dxt = tp['dgrad1'].run(dpre, (h, w))
+        if 'shortcut' in tp:
+            g['shortcut_layer.1.bias'], g['shortcut_layer.1.weight'] = bt.backward_reduce(dout, sc_raw, st_s)
+            dsr = bt.backward_apply(dout, sc_raw, st_s, g['shortcut_layer.1.bias'], g['shortcut_layer.1.weight'])
+            g['shortcut_layer.0.weight'] = wgrad(x, dsr, 1, self.stride)
+            addend = tp['dshortcut'].run(dsr, (h, w))
+        else:
+            addend = dsc if identity_s2 else dout
+        g['res_layer.0.bias'], g['res_layer.0.weight'] = bt.backward_reduce(dxt, x, st1)
+        if post is None:
+            return bt.backward_apply(dxt, x, st1, g['res_layer.0.bias'], g['res_layer.0.weight'], addend=addend), g
+        return bt.backward_apply(dxt, x, st1, g['res_layer.0.bias'], g['res_layer.0.weight'], addend=addend, act=post[0], slope=post[1], want_raw=True), g
 
 
 class bottleneck_IR(_ResidualUnit):  # noqa: N801  (reference class name)

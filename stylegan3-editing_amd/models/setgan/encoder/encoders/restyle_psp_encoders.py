@@ -2,7 +2,8 @@
 
 `BackboneEncoder` (:10-50): conv3x3(input_nc -> 64) + BN + PReLU at 256^2, the IR / IR-SE stages down to [N,512,16,16],
 then `n_styles` GradualStyleBlock heads, stacked to [N, n_styles, 512].  Module names and therefore state_dict keys are
-the reference's.  In eval mode on a GPU the backbone runs on libsg3hip's matrix-core convolution with BatchNorm / PReLU
+the reference's.  Training goes through PyTorch autograd by default; `native_training = True` runs the trunk's train-mode forward
+and backward (batch-statistic BatchNorm, weight and data gradients) on libsg3hip as one autograd node, the heads stay on torch.  In eval mode on a GPU the backbone runs on libsg3hip's matrix-core convolution with BatchNorm / PReLU
 fused; the first level of all style heads as one strip convolution on the same kernel, the deeper levels (tiny maps,
 weight-bandwidth bound) as batched GEMMs over all heads on patches written by `sg3_unfold3x3s2`.
 `ResNetBackboneEncoder` (:53-97): the same heads on a ResNet34 trunk (7x7 stride-2 stem without max-pool, then torchvision's
@@ -169,7 +170,35 @@ class _StyleHeadEncoder(Module):
         return self._forward_torch(x)
 
 
+class _TrunkTrain(torch.autograd.Function):
+    """The trunk of a `BackboneEncoder` in train mode as ONE autograd node on libsg3hip: inputs are the image and the trunk's
+    parameters (in `_trunk_named_parameters` order), the output is the [N,512,h,w] map the style heads read.  The forward keeps the
+    activations, batch statistics and the packs it ran on; the backward returns a gradient for every trunk parameter and, when it
+    is needed, for the image."""
+
+    @staticmethod
+    def forward(ctx, enc, x, *params):
+        out, ctx.saved = enc._trunk_train_forward(x.detach())
+        ctx.enc = enc
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        dx, grads = ctx.enc._trunk_train_backward(ctx.saved, dout, ctx.needs_input_grad[1])
+        return (None, dx) + tuple(grads[name] for name, _ in ctx.enc._trunk_named_parameters())
+
+
 class BackboneEncoder(_StyleHeadEncoder):
+    # Train mode on libsg3hip: with this on, a CUDA float32 input, `self.training` and grad enabled, stem and `body` run as one
+    # autograd node (`_TrunkTrain`: batch-statistic BatchNorm, native weight / data gradients); the style heads stay torch modules under
+    # autograd.  Off (the default), training takes `_forward_torch` as before.
+    native_training = False
+    # Arithmetic of the recorded training forward's convolutions: 'fp32' (exact products, four accumulation chains) by default --
+    # under 'f16x3' the trunk's parameter gradients measured up to 20 x the float32-autograd error (DESIGN.md 3.15); 'f16x3' opts in,
+    # with the overflow repeat on the exact kernels.  The eval-mode forward keeps following `plain_conv.precision`.
+    native_training_precision = 'fp32'
+
     def __init__(self, num_layers, mode='ir', n_styles=18, opts=None):
         super().__init__()
         assert num_layers in [50, 100, 152], 'num_layers should be 50,100, or 152'
@@ -182,6 +211,82 @@ class BackboneEncoder(_StyleHeadEncoder):
 
     def _trunk_torch(self, x):
         return self.body(self.input_layer(x))
+
+    # ---- native training of the trunk ----
+    def _forward_torch(self, x):
+        if self.native_training and self.training and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32:
+            feat = _TrunkTrain.apply(self, x, *[p for _, p in self._trunk_named_parameters()])
+            return self._combine([style(feat) for style in self.styles])
+        return super()._forward_torch(x)
+
+    def _trunk_named_parameters(self):
+        return [(f'{prefix}.{n}', p) for prefix in ('input_layer', 'body') for n, p in getattr(self, prefix).named_parameters()]
+
+    def _stem_train_pack(self):
+        w = self.input_layer[0].weight
+        key = (w.data_ptr(), w._version)
+        sp = getattr(self, '_stem_train_packed', None)
+        if sp is None or sp['key'] != key:
+            from torch_utils.ops.plain_conv import ACT_NONE, PackedConv
+            from torch_utils.ops.plain_conv_grad import PackedDgrad
+            sp = self._stem_train_packed = dict(key=key, conv=PackedConv(w, act=ACT_NONE, stride=1, padding=1, chains=True), dgrad=PackedDgrad(w, stride=1))
+        return sp
+
+    def _trunk_train_record(self, x):
+        from torch_utils.ops import batchnorm_train as bt
+        _, bn, prelu = self.input_layer
+        sp = self._stem_train_pack()
+        pairs = []
+        c0 = sp['conv'].run(x)
+        st0 = bt.stats(c0, bn.weight, bn.bias, bn.eps)
+        h, pre0 = bt.apply(c0, st0.a, bn.bias, centre=st0.mean, centre_lo=st0.mean_lo, slope=prelu.weight, want_pre=True)
+        pairs.append((bn, st0))
+        units = []
+        for unit in self.body:
+            h, sv = unit.forward_train_record(h, pairs)
+            units.append(sv)
+        return h, (x, c0, st0, pre0, prelu.weight.detach().to(torch.float32).contiguous(), sp, units), pairs
+
+    def _trunk_train_forward(self, x):
+        """Stem (convolution, BatchNorm statistics, apply + PReLU: three ABI calls) and every unit's `forward_train_record`.  The
+        convolutions run under `native_training_precision`; a split-precision forward that met an operand outside the fp16 range is repeated
+        on the exact fp32 kernels, and only the accepted forward's statistics reach the running buffers (one fused update)."""
+        from torch_utils.ops import batchnorm_train as bt
+        from torch_utils.ops import plain_conv
+        assert self.native_training_precision in ('fp32', 'f16x3')
+        x = x.contiguous()
+        kept, plain_conv.precision = plain_conv.precision, self.native_training_precision
+        try:
+            plain_conv.reset_overflow(x.device)
+            out, saved, pairs = self._trunk_train_record(x)
+            if plain_conv.precision != 'fp32' and plain_conv.overflowed(x.device):
+                plain_conv.precision = 'fp32'
+                out, saved, pairs = self._trunk_train_record(x)
+        finally:
+            plain_conv.precision = kept
+        bt.update_running([bn for bn, _ in pairs], [st for _, st in pairs])
+        return out, saved
+
+    def _trunk_train_backward(self, saved, dout, need_dx):
+        """Units last to first, then the stem: its slope gradient (from the unmasked gradient unit 0 hands back), BatchNorm backward,
+        weight gradient, and the data gradient when the image needs one: four ABI calls, five with it.  -> (dx | None, {name: grad})"""
+        from torch_utils.ops import batchnorm_train as bt
+        from torch_utils.ops.plain_conv_wgrad import wgrad
+        x, c0, st0, pre0, slope0, sp, units = saved
+        grads = {}
+        d, raw = dout.contiguous(), None
+        for idx in reversed(range(len(units))):
+            if idx == 0:
+                (d, raw), g = self.body[idx].backward_train(units[idx], d, post=(pre0, slope0))
+            else:
+                d, g = self.body[idx].backward_train(units[idx], d)
+            grads.update({f'body.{idx}.{k}': v for k, v in g.items()})
+        grads['input_layer.2.weight'] = bt.slope_grad(raw, pre0)
+        grads['input_layer.1.bias'], grads['input_layer.1.weight'] = bt.backward_reduce(d, c0, st0)
+        dc0 = bt.backward_apply(d, c0, st0, grads['input_layer.1.bias'], grads['input_layer.1.weight'])
+        grads['input_layer.0.weight'] = wgrad(x, dc0, 3, 1)
+        dx = sp['dgrad'].run(dc0, (int(x.shape[2]), int(x.shape[3]))) if need_dx else None
+        return dx, grads
 
     def _pack_trunk(self, pk):
         from torch_utils.ops.plain_conv import ACT_PRELU, PackedConv, bn_affine

@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get('SG3_LIB') or os.path.join(_PKG_ROOT, 'lib', 'libsg3hi
 
 SG3_OK, SG3_NO_KERNEL, SG3_BAD_ARG, SG3_HIP_ERROR = 0, -1, -2, -3
 SG3_F32, SG3_F16, SG3_F64 = 0, 1, 2
-SG3_CONV_FP32, SG3_CONV_F16X3, SG3_CONV_F16, SG3_CONV_F16X3_F23, SG3_CONV_F16_F23 = 0, 1, 2, 3, 4
+SG3_CONV_FP32, SG3_CONV_F16X3, SG3_CONV_F16, SG3_CONV_F16X3_F23, SG3_CONV_F16_F23, SG3_CONV_FP32_CHAINS = 0, 1, 2, 3, 4, 5
 SG3_MODCONV_FP32_MFMA, SG3_MODCONV_TORGB, SG3_MODCONV_ROWS, SG3_MODCONV_FLAT, SG3_MODCONV_GEMM1, SG3_MODCONV_F23 = range(6)   # sg3_modconv_dispatch_info.family
 SG3_FLRELU_NONE, SG3_FLRELU_POINTWISE, SG3_FLRELU_STREAM = range(3)                             # sg3_filtered_lrelu_dispatch_info.kind
 SG3_CONV2D_FORM_F16X3 = 16          # sg3_conv2d_form: first f16x3 form (include/sg3_ops.h)
@@ -257,6 +257,32 @@ class LpipsHeadParams(ctypes.Structure):
                 ('N', c_i32), ('C', c_i32), ('h', c_i32), ('w', c_i32), ('reluMask', c_i32)]
 
 
+class Conv2dWgradSumParams(ctypes.Structure):
+    _fields_ = [('x', c_vp), ('dy', c_vp), ('inScale', c_vp), ('inShift', c_vp), ('dw', c_vp), ('partial', c_vp),
+                ('N', c_i32), ('I', c_i32), ('O', c_i32), ('H', c_i32), ('W', c_i32), ('k', c_i32), ('stride', c_i32)]
+
+
+class BnTrainStatsParams(ctypes.Structure):
+    _fields_ = [('x', c_vp), ('gamma', c_vp), ('beta', c_vp), ('partial', c_vp), ('mean', c_vp), ('meanLo', c_vp), ('var', c_vp), ('invstd', c_vp), ('a', c_vp), ('b', c_vp),
+                ('N', c_i32), ('C', c_i32), ('H', c_i32), ('W', c_i32), ('eps', c_f32)]
+
+
+class BnTrainApplyParams(ctypes.Structure):
+    _fields_ = [('x', c_vp), ('scale', c_vp), ('shift', c_vp), ('centre', c_vp), ('centreLo', c_vp), ('slope', c_vp), ('y', c_vp), ('pre', c_vp),
+                ('N', c_i32), ('C', c_i32), ('H', c_i32), ('W', c_i32)]
+
+
+class BnTrainBwdReduceParams(ctypes.Structure):
+    _fields_ = [('dy', c_vp), ('x', c_vp), ('mean', c_vp), ('meanLo', c_vp), ('invstd', c_vp), ('slope', c_vp), ('masked', c_vp), ('partial', c_vp), ('sum1', c_vp), ('sum2', c_vp),
+                ('N', c_i32), ('C', c_i32), ('H', c_i32), ('W', c_i32), ('mode', c_i32)]
+
+
+class BnTrainBwdApplyParams(ctypes.Structure):
+    _fields_ = [('dy', c_vp), ('x', c_vp), ('mean', c_vp), ('meanLo', c_vp), ('invstd', c_vp), ('scale', c_vp), ('sum1', c_vp), ('sum2', c_vp),
+                ('addend', c_vp), ('addStride', c_i64 * 4), ('act', c_vp), ('slope', c_vp), ('dx', c_vp), ('raw', c_vp),
+                ('N', c_i32), ('C', c_i32), ('H', c_i32), ('W', c_i32)]
+
+
 # every symbol include/sg3_ops.h declares: (name, restype, argtypes)
 EXPORTS = [
     ('sg3_abi_version', ctypes.c_int, []),
@@ -328,6 +354,13 @@ EXPORTS = [
     ('sg3_maxpool3s2_bwd', ctypes.c_int, [ctypes.POINTER(Maxpool3s2BwdParams), c_vp]),
     ('sg3_lpips_head_blocks', ctypes.c_int, [ctypes.c_int] * 2),
     ('sg3_lpips_head', ctypes.c_int, [ctypes.POINTER(LpipsHeadParams), c_vp]),
+    ('sg3_conv2d_wgrad_sum_splits', ctypes.c_int, [ctypes.c_int] * 7 + [ctypes.POINTER(ctypes.c_int)] * 3),
+    ('sg3_conv2d_wgrad_sum', ctypes.c_int, [ctypes.POINTER(Conv2dWgradSumParams), c_vp]),
+    ('sg3_bn_train_partials', ctypes.c_int, [ctypes.c_int] * 3),
+    ('sg3_bn_train_stats', ctypes.c_int, [ctypes.POINTER(BnTrainStatsParams), c_vp]),
+    ('sg3_bn_train_apply', ctypes.c_int, [ctypes.POINTER(BnTrainApplyParams), c_vp]),
+    ('sg3_bn_train_bwd_reduce', ctypes.c_int, [ctypes.POINTER(BnTrainBwdReduceParams), c_vp]),
+    ('sg3_bn_train_bwd_apply', ctypes.c_int, [ctypes.POINTER(BnTrainBwdApplyParams), c_vp]),
 ]
 
 _lib = None

@@ -4,7 +4,9 @@ zero padding stays zero), a BatchNorm behind (folded into the packed weights and
 
 Replaces, for inference, the module calls Conv2d / BatchNorm2d / PReLU / LeakyReLU of the IR-SE50 backbone and the
 GradualStyleBlock heads (reference models/setgan/encoder/encoders/helpers.py:98-120, restyle_psp_encoders.py:26-50,
-map2style.py:15-24).  Inference only: no autograd (training the encoder is out of scope).
+map2style.py:15-24).  No autograd here: training the encoder trunk records these forwards and differentiates them by hand with
+plain_conv_grad.py (data gradient), plain_conv_wgrad.py (weight gradient) and batchnorm_train.py; there the BatchNorm in front is the
+batch's, handed to `run` per call, and nothing is folded into the packed weights.
 """
 import ctypes
 
@@ -47,7 +49,10 @@ class PackedConv:
     """Weights of one convolution in the implicit-GEMM operand layout, plus its fused epilogue / prologue vectors."""
 
     def __init__(self, weight, out_scale=None, bias=None, in_scale=None, in_shift=None, act=ACT_NONE, slope=None, stride=1, padding=0,
-                 precision=None):
+                 precision=None, chains=False):
+        # `chains`: the exact-fp32 form of this object accumulates every output in four chains instead of one (SG3_CONV_FP32_CHAINS: the
+        # recorded training forward, whose error would otherwise grow with the 24 units it passes through; same pack)
+        self.chains = bool(chains)
         # `precision`: 'fp32' / 'f16x3' for this object whatever the module-wide `precision` says (the LPIPS criterion runs exact fp32);
         # None follows the module-wide setting at every call
         assert precision in (None, 'fp32', 'f16x3')
@@ -84,14 +89,17 @@ class PackedConv:
     def __call__(self, x):
         return self.run(x)
 
-    def _params(self, x, out):
+    def _params(self, x, out, in_scale=None, in_shift=None):
         split = (self.precision or precision) == 'f16x3'
         prec = abi.SG3_CONV_F16X3 if split else abi.SG3_CONV_FP32
         n, _, h, w = (int(v) for v in x.shape)
         p = abi.Conv2dParams()
         p.x, p.wPacked, p.out = abi.ptr(x), abi.ptr(self.packed(prec)), abi.ptr(out)
         p.precision, p.rangeFlag, p.wScale = prec, (abi.ptr(_flag(x.device)) if split else None), abi.ptr(self._scales[prec])
-        p.inScale, p.inShift, p.bias, p.slope = abi.ptr(self.in_scale), abi.ptr(self.in_shift), abi.ptr(self.bias), abi.ptr(self.slope)
+        if self.chains and not split:
+            p.precision = abi.SG3_CONV_FP32_CHAINS
+        p.inScale, p.inShift = abi.ptr(self.in_scale if in_scale is None else in_scale), abi.ptr(self.in_shift if in_shift is None else in_shift)
+        p.bias, p.slope = abi.ptr(self.bias), abi.ptr(self.slope)
         p.N, p.I, p.O, p.H, p.W = n, self.I, self.O, h, w
         p.k, p.stride, p.pad, p.act = self.k, self.stride, self.padding, self.act
         return p
@@ -103,14 +111,18 @@ class PackedConv:
         with torch.cuda.device(x.device):
             return int(abi.load().sg3_conv2d_form(ctypes.byref(self._params(x, x))))
 
-    def run(self, x):
+    def run(self, x, in_scale=None, in_shift=None):
+        """`in_scale` / `in_shift` [I] float32 contiguous on x's device: this call's input affine in place of the object's own (a train-mode
+        BatchNorm in front, whose statistics belong to the batch)."""
         assert x.is_cuda and x.dtype == torch.float32 and x.ndim == 4 and x.shape[1] == self.I
+        assert (in_scale is None) == (in_shift is None) and (in_scale is None or (in_scale.numel() == in_shift.numel() == self.I and in_scale.is_contiguous()
+                                                                                  and in_shift.is_contiguous() and in_scale.dtype == in_shift.dtype == torch.float32))
         x = x.contiguous()
         n, _, h, w = (int(v) for v in x.shape)
         oh = (h + 2 * self.padding - self.k) // self.stride + 1
         ow = (w + 2 * self.padding - self.k) // self.stride + 1
         out = torch.empty([n, self.O, oh, ow], dtype=torch.float32, device=x.device)
-        p = self._params(x, out)
+        p = self._params(x, out, in_scale, in_shift)
         with torch.cuda.device(x.device):
             abi.check(abi.load().sg3_conv2d(ctypes.byref(p), abi.stream_ptr(x.device)), 'sg3_conv2d')
         return out

@@ -51,7 +51,31 @@ def se_residual_record(res, shortcut, fc1_weight, fc2_weight):
 
 
 def se_residual_bwd(dout, res, mean, fc1_weight, fc2_weight, scatter_hw=None):
-    """Backward of `se_residual_record` (csrc/sg3_se_bwd.hip, two launches) -> (dres, dscatter).  The shortcut's gradient is `dout`
+    """Backward of `se_residual_record` with respect to res and the shortcut -> (dres, dscatter); see `_backward`."""
+    return _backward(dout, res, mean, fc1_weight, fc2_weight, scatter_hw)[:2]
+
+
+def se_residual_bwd_train(dout, res, mean, fc1_weight, fc2_weight, scatter_hw=None):
+    """`se_residual_bwd` that also hands out dg [N,C] = sum_hw dout * res, the gate's upstream gradient the first launch leaves in
+    its scratch: with the saved mean it gives the gradients of fc1 and fc2 as two small matrix products (`se_weight_grads`)."""
+    return _backward(dout, res, mean, fc1_weight, fc2_weight, scatter_hw)
+
+
+def se_weight_grads(dg, mean, fc1_weight, fc2_weight):
+    """(dfc1, dfc2) of gate = sigmoid(fc2 relu(fc1 mean)) from dg = dL/dgate [N,C] and the saved plane means [N,C].  Plain torch on
+    [N,C] / [N,R] tensors: the gate is recomputed from the mean (two matrix products, relu, sigmoid) rather than saved, then the two
+    matrix products of the gradients; about nine small launches that the units' ABI-call counts do not include."""
+    w1, w2 = fc1_weight.detach().flatten(1), fc2_weight.detach().flatten(1)
+    u_pre = mean @ w1.t()
+    u = torch.relu(u_pre)
+    g = torch.sigmoid(u @ w2.t())
+    dz = dg * g * (1 - g)
+    du = (dz @ w2) * (u_pre > 0)
+    return (du.t() @ mean).view_as(fc1_weight), (dz.t() @ u).view_as(fc2_weight)
+
+
+def _backward(dout, res, mean, fc1_weight, fc2_weight, scatter_hw):
+    """Backward of `se_residual_record` (csrc/sg3_se_bwd.hip, two launches) -> (dres, dscatter, dg).  The shortcut's gradient is `dout`
     itself; with `scatter_hw` = (inH, inW), the size of the input an identity shortcut subsampled by 2, dscatter [N,C,inH,inW] is
     dout at the even positions and zero elsewhere (else None)."""
     if not (dout.is_cuda and dout.dtype == torch.float32 and res.dtype == torch.float32 and res.is_contiguous() and tuple(res.shape) == tuple(dout.shape)):
@@ -73,4 +97,4 @@ def se_residual_bwd(dout, res, mean, fc1_weight, fc2_weight, scatter_hw=None):
     p.N, p.C, p.H, p.W, p.R = n, c, h, w, r
     with torch.cuda.device(res.device):
         abi.check(abi.load().sg3_se_residual_bwd(ctypes.byref(p), abi.stream_ptr(res.device)), 'sg3_se_residual_bwd')
-    return dres, dsc
+    return dres, dsc, dg
