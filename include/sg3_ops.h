@@ -580,7 +580,8 @@ typedef struct sg3_conv2d_params {
 
 SG3_API int sg3_conv2d(const sg3_conv2d_params* p, void* stream);
 
-/* Diagnostic: the kernel form sg3_conv2d launches for *p (same checks, nothing launched; negative status for invalid params).
+/* Diagnostic: the kernel form sg3_conv2d launches for *p (same checks, nothing launched; negative status for invalid params): the
+ * `form` field of sg3_conv2d_dispatch (below, with tile, grid and LDS of the launch) for the current device.
  *   SG3_CONV_FP32_CHAINS:  12 (64 ch x 2 rows) or 13 (32 ch x 4 rows)
  *   SG3_CONV_FP32:  ((k == 3) * 2 + (stride == 2)) * 3 + tile, tile 0 = 128 ch x 4 rows, 1 = 64 ch x 2 rows, 2 = 32 ch x 4 rows
  *                   (12 forms);
@@ -1212,6 +1213,40 @@ typedef struct sg3_conv2d_wgrad_sum_params {
 
 SG3_API int sg3_conv2d_wgrad_sum_splits(int N, int I, int O, int H, int W, int k, int stride, int* nSplit, int* chunksPerSplit, int* xSegs);
 SG3_API int sg3_conv2d_wgrad_sum(const sg3_conv2d_wgrad_sum_params* p, void* stream);
+
+/* ----------------------------------------------------------------------
+ * What sg3_conv2d, sg3_conv2d_dgrad and sg3_conv2d_wgrad_sum launch for a call: kernel family, template coordinates, geometry and launch
+ * values, from the functions the launches themselves use (csrc/sg3_conv2d_plan.h).  Fields a family has no use for are 0.
+ * ---------------------------------------------------------------------- */
+enum {
+    SG3_CONV2D_FP32_MFMA = 0,  /* conv2d_mfma_kernel<KS, STRIDE, WM, WN, TM, TN, CHAINS>: exact fp32 products */
+    SG3_CONV2D_F16X3     = 1,  /* conv2d_f16x3_kernel<KS, STRIDE, WM, WN, TM, TN>: fp16 hi/lo operands */
+    SG3_CONV2D_DGRAD     = 2,  /* conv2d_dgrad_kernel<KS, STRIDE, WM, WN, TM, TN> */
+    SG3_CONV2D_WGRAD_SUM = 3,  /* conv2d_wgrad_sum_kernel<KS, STRIDE>, then conv2d_wgrad_sum_reduce_kernel when nSplit > 1 */
+};
+
+typedef struct sg3_conv2d_dispatch_info {
+    int32_t        family;     /* SG3_CONV2D_* */
+    int32_t        form;       /* forward: what sg3_conv2d_form returns; -1 otherwise */
+    int32_t        KS, STRIDE, WM, WN, TM, TN;   /* a workgroup takes 32 WM TM channels x (WN TN rows x 32 columns) */
+    int32_t        CHAINS;     /* FP32_MFMA: accumulators per output (1 | 4) */
+    int32_t        kc, nch;    /* channels per K chunk, K chunks (dgrad: of the output channels) */
+    int32_t        outH, outW; /* size of the forward's output (dgrad, wgrad_sum: of dy) */
+    int32_t        xTiles, yTiles, mTiles;
+    int32_t        classes;    /* dgrad: pixel parity classes, stride^2, each with tiles of its own */
+    int32_t        xSegs, nChunks, nSplit, chunksPerSplit;   /* wgrad_sum: as sg3_conv2d_wgrad_sum_splits describes them */
+    int32_t        oTiles, iTiles;   /* wgrad_sum: 64 x 64 (o, i) tiles */
+    int32_t        reduceGrid; /* wgrad_sum: workgroups (of 256) of the reduce launch, 0 with one split */
+    int32_t        totalBlocks; /* the grid: xTiles yTiles mTiles N (x classes) | oTiles iTiles nSplit */
+    int32_t        block;
+    int32_t        ldsBytes;   /* dynamic LDS of the launch (0: the kernel's LDS is static) */
+} sg3_conv2d_dispatch_info;
+
+/* Host only: no launch, no pointer followed (only whether a pointer is set is read, so placeholders do).  SG3_BAD_ARG for a call the
+ * launch rejects, a grid past 2^31 - 1 workgroups included.  `cus` <= 0: the CU count of the current device, 256 without one. */
+SG3_API int sg3_conv2d_dispatch(const sg3_conv2d_params* p, int cus, sg3_conv2d_dispatch_info* out);
+SG3_API int sg3_conv2d_dgrad_dispatch(const sg3_conv2d_dgrad_params* p, sg3_conv2d_dispatch_info* out);
+SG3_API int sg3_conv2d_wgrad_sum_dispatch(const sg3_conv2d_wgrad_sum_params* p, sg3_conv2d_dispatch_info* out);
 
 /* ----------------------------------------------------------------------
  * Training-mode BatchNorm2d (csrc/sg3_bn_train.hip).  Contiguous float32 [N][C][H][W]; per-channel vectors [C]; float64 sums in a

@@ -8,7 +8,7 @@
 // global->registers during the MFMA loop.  Differences: stride 1 or 2; a per-input-channel affine (the BatchNorm that
 // precedes the first convolution of a bottleneck) applied while staging, only inside the image so zero padding stays
 // zero; epilogue bias (folded BatchNorm / conv bias) and PReLU / leaky ReLU.
-#include "sg3_igemm_f32.h"
+#include "sg3_conv2d_plan.h"
 #include "sg3_split.h"
 
 namespace sg3 {
@@ -463,88 +463,45 @@ conv2d_pack_f16x3_kernel(const float* w, const float* outScale, float* wp, float
     }
 }
 
-// The kernel parameters of a call on BM-channel x (ROWS rows x 32 columns) tiles with K chunks of kc channels
-static int plain_params(const sg3_conv2d_params& q, int BM, int ROWS, int kc, PlainConvParams& p) {
+// The kernel parameters of a planned call
+static PlainConvParams plain_params(const sg3_conv2d_params& q, const Conv2dPlan& pl) {
+    PlainConvParams p;
     p.x = q.x; p.wp = q.wPacked; p.inScale = q.inScale; p.inShift = q.inShift; p.bias = q.bias; p.slope = q.slope; p.out = q.out;
     p.wScale = q.wScale;
     p.N = q.N; p.I = q.I; p.O = q.O; p.H = q.H; p.W = q.W; p.stride = q.stride; p.pad = q.pad; p.act = q.act;
-    p.outH = (q.H + 2 * q.pad - q.k) / q.stride + 1; p.outW = (q.W + 2 * q.pad - q.k) / q.stride + 1;
-    p.nch = ceil_div(q.I, kc);
-    p.xTiles = ceil_div(p.outW, 32); p.yTiles = ceil_div(p.outH, ROWS); p.mTiles = ceil_div(q.O, BM);
-    const long long total = (long long)p.xTiles * p.yTiles * p.mTiles * q.N;
-    if (total > 0x7fffffffLL) { set_error("conv2d: grid too large"); return SG3_BAD_ARG; }
-    p.totalBlocks = (int)total;
-    return SG3_OK;
+    p.outH = pl.outH; p.outW = pl.outW; p.nch = pl.nch; p.xTiles = pl.xTiles; p.yTiles = pl.yTiles; p.mTiles = pl.mTiles; p.totalBlocks = pl.totalBlocks;
+    return p;
 }
 
 template <int KS, int STRIDE, int WM, int WN, int TM, int TN>
-static int launch_plain_f16x3(const sg3_conv2d_params& q, hipStream_t st) {
-    constexpr int BM = WM * TM * 32, ROWS = WN * TN;
-    constexpr size_t ldsBytes = ((size_t)BM * (KS * KS * 32 + 8) + 4 * (size_t)((ROWS - 1) * STRIDE + KS) * (31 * STRIDE + KS) * 8) * sizeof(_Float16);
-    PlainConvParams p;
-    const int rc = plain_params(q, BM, ROWS, 16, p);
-    if (rc != SG3_OK) return rc;
+static int launch_plain_f16x3(const sg3_conv2d_params& q, const Conv2dPlan& pl, hipStream_t st) {
     auto kern = conv2d_f16x3_kernel<KS, STRIDE, WM, WN, TM, TN>;
-    if (ldsBytes > 64 * 1024)
-        SG3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes));
-    hipLaunchKernelGGL(kern, dim3((unsigned)p.totalBlocks), dim3(256), ldsBytes, st, p, q.rangeFlag);
+    if (pl.ldsBytes > 64 * 1024)
+        SG3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, pl.ldsBytes));
+    hipLaunchKernelGGL(kern, dim3((unsigned)pl.totalBlocks), dim3(pl.block), (size_t)pl.ldsBytes, st, plain_params(q, pl), q.rangeFlag);
     SG3_LAUNCH_CHECK("conv2d_f16x3_kernel");
     return SG3_OK;
 }
 
-// The branch of dispatch_plain_f16x3 a call takes (SG3_CONV2D_FORM_F16X3 + 0 .. 5, see sg3_conv2d_form)
-static int plain_f16x3_form(const sg3_conv2d_params& q) {
-    if (q.k == 1) return q.stride == 2 ? 0 : 1;                                     // the projection shortcuts: same kernel, one tap
-    if (q.stride == 2) return 2;                                                     // 64 x (4 rows x 32), 9 x 65 patch
-    const int outH = q.H + 2 * q.pad - 2, outW = q.W + 2 * q.pad - 2;
-    if (outH <= 16) return 3;                                                        // 64 x (4 rows x 32): the 16x16 maps
-    // The 8-row tile (230 registers: two workgroups per CU) needs a grid that offers every CU its two workgroups; the 32 x 32 maps
-    // of a 16-frame batch (14 units of the IR-SE50 trunk, 28 launches) give 256 eight-row tiles = ONE four-wave workgroup per CU
-    // (counters, round 4: 0.85 waves per SIMD, matrix pipes 0.32 busy at 2.45 GHz -- latency, not power).  Such grids take the
-    // 4-row tile instead (153 registers, three workgroups per CU): twice the workgroups, each with half the rows.
-    const long long tiles8 = (long long)q.N * ceil_div(q.O, 64) * ceil_div(outH, 8) * ceil_div(outW, 32);
-    if (tiles8 < 2 * (long long)device_cu_count()) return 4;
-    return 5;                                                                        // 64 x (8 rows x 32)
-}
-
-static int dispatch_plain_f16x3(const sg3_conv2d_params& q, hipStream_t st) {
-    switch (plain_f16x3_form(q)) {
-    case 0: return launch_plain_f16x3<1, 2, 1, 4, 2, 1>(q, st);
-    case 1: return launch_plain_f16x3<1, 1, 1, 4, 2, 1>(q, st);
-    case 2: return launch_plain_f16x3<3, 2, 1, 4, 2, 1>(q, st);
-    case 3: case 4: return launch_plain_f16x3<3, 1, 1, 4, 2, 1>(q, st);
-    default: return launch_plain_f16x3<3, 1, 1, 4, 2, 2>(q, st);
-    }
-}
-
-template <int KS, int STRIDE, int WM, int WN, int TM, int TN, int CHAINS = 1>
-static int launch_plain(const sg3_conv2d_params& q, hipStream_t st) {
-    PlainConvParams p;
-    const int rc = plain_params(q, WM * TM * 32, WN * TN, ConvK<KS>::KC, p);
-    if (rc != SG3_OK) return rc;
-    hipLaunchKernelGGL((conv2d_mfma_kernel<KS, STRIDE, WM, WN, TM, TN, CHAINS>), dim3((unsigned)p.totalBlocks), dim3(256), 0, st, p);
+template <int KS, int STRIDE, int WM, int WN, int TM, int TN, int CHAINS>
+static int launch_plain(const sg3_conv2d_params& q, const Conv2dPlan& pl, hipStream_t st) {
+    hipLaunchKernelGGL((conv2d_mfma_kernel<KS, STRIDE, WM, WN, TM, TN, CHAINS>), dim3((unsigned)pl.totalBlocks), dim3(pl.block), 0, st, plain_params(q, pl));
     SG3_LAUNCH_CHECK("conv2d_mfma_kernel");
     return SG3_OK;
 }
 
-// The tile of dispatch_plain a call takes: small feature maps (16x16 and below) get the 4-row tile, large ones the 128-channel
-// tile when O allows
-static int plain_tile(const sg3_conv2d_params& q) {
-    const int outH = (q.H + 2 * q.pad - q.k) / q.stride + 1;
-    if (q.O >= 128 && outH >= 8) return 0;                                   // 128 x (4 rows x 32)
-    if (q.O > 32) return 1;                                                  // 64 x (2 rows x 32)
-    return 2;                                                                // 32 x (4 rows x 32)
+// plan coordinates -> template instantiation: the five f16x3 kernels; per (KS, STRIDE) the two tiles with four chains, the three with one
+static int launch_f16x3_tile(const sg3_conv2d_params& q, const Conv2dPlan& pl, hipStream_t st) {
+    if (pl.KS == 1) return pl.STRIDE == 2 ? launch_plain_f16x3<1, 2, 1, 4, 2, 1>(q, pl, st) : launch_plain_f16x3<1, 1, 1, 4, 2, 1>(q, pl, st);
+    if (pl.STRIDE == 2) return launch_plain_f16x3<3, 2, 1, 4, 2, 1>(q, pl, st);
+    return pl.TN == 1 ? launch_plain_f16x3<3, 1, 1, 4, 2, 1>(q, pl, st) : launch_plain_f16x3<3, 1, 1, 4, 2, 2>(q, pl, st);
 }
 
 template <int KS, int STRIDE>
-static int dispatch_plain(const sg3_conv2d_params& q, hipStream_t st) {
-    if (q.precision == SG3_CONV_FP32_CHAINS)             // four accumulators per tile: the 64- and 32-channel tiles only
-        return q.O > 32 ? launch_plain<KS, STRIDE, 2, 2, 1, 1, 4>(q, st) : launch_plain<KS, STRIDE, 1, 4, 1, 1, 4>(q, st);
-    switch (plain_tile(q)) {
-    case 0: return launch_plain<KS, STRIDE, 2, 2, 2, 2>(q, st);
-    case 1: return launch_plain<KS, STRIDE, 2, 2, 1, 1>(q, st);
-    default: return launch_plain<KS, STRIDE, 1, 4, 1, 1>(q, st);
-    }
+static int launch_tile(const sg3_conv2d_params& q, const Conv2dPlan& pl, hipStream_t st) {
+    if (pl.CHAINS == 4) return pl.WM == 2 ? launch_plain<KS, STRIDE, 2, 2, 1, 1, 4>(q, pl, st) : launch_plain<KS, STRIDE, 1, 4, 1, 1, 4>(q, pl, st);
+    if (pl.TM == 2) return launch_plain<KS, STRIDE, 2, 2, 2, 2, 1>(q, pl, st);
+    return pl.WM == 2 ? launch_plain<KS, STRIDE, 2, 2, 1, 1, 1>(q, pl, st) : launch_plain<KS, STRIDE, 1, 4, 1, 1, 1>(q, pl, st);
 }
 
 } // namespace sg3
@@ -588,22 +545,30 @@ static int check_conv2d(const sg3_conv2d_params* p) {
 }
 
 int sg3_conv2d_form(const sg3_conv2d_params* p) {
+    const int rc = check_conv2d(p);
+    return rc != SG3_OK ? rc : sg3::plan_conv2d(*p, sg3::device_cu_count()).form;
+}
+
+// the checks and the plan of the launch
+int sg3_conv2d_dispatch(const sg3_conv2d_params* p, int cus, sg3_conv2d_dispatch_info* out) {
     using namespace sg3;
+    SG3_REQUIRE(out, "conv2d_dispatch: null argument");
     const int rc = check_conv2d(p);
     if (rc != SG3_OK) return rc;
-    if (p->precision == SG3_CONV_F16X3) return SG3_CONV2D_FORM_F16X3 + plain_f16x3_form(*p);
-    if (p->precision == SG3_CONV_FP32_CHAINS) return 12 + (p->O > 32 ? 0 : 1);
-    return ((p->k == 3 ? 2 : 0) + (p->stride == 2 ? 1 : 0)) * 3 + plain_tile(*p);
+    *out = plan_conv2d(*p, cus > 0 ? cus : device_cu_count());
+    SG3_REQUIRE(out->totalBlocks > 0, "conv2d: grid too large");
+    return SG3_OK;
 }
 
 int sg3_conv2d(const sg3_conv2d_params* p, void* stream) {
     using namespace sg3;
-    const int rc = check_conv2d(p);
+    Conv2dPlan pl;
+    const int rc = sg3_conv2d_dispatch(p, 0, &pl);
     if (rc != SG3_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (p->precision == SG3_CONV_F16X3) return dispatch_plain_f16x3(*p, st);
-    if (p->k == 3) return p->stride == 1 ? dispatch_plain<3, 1>(*p, st) : dispatch_plain<3, 2>(*p, st);
-    return p->stride == 1 ? dispatch_plain<1, 1>(*p, st) : dispatch_plain<1, 2>(*p, st);
+    if (pl.family == SG3_CONV2D_F16X3) return launch_f16x3_tile(*p, pl, st);
+    if (p->k == 3) return p->stride == 1 ? launch_tile<3, 1>(*p, pl, st) : launch_tile<3, 2>(*p, pl, st);
+    return p->stride == 1 ? launch_tile<1, 1>(*p, pl, st) : launch_tile<1, 2>(*p, pl, st);
 }
 
 } // extern "C"

@@ -16,7 +16,7 @@
 // Epilogue, per written element:  v = acc (+ addend, through element strides);  v *= (act > 0 ? 1 : slope[i])  when `act` is given
 // (the derivative of the PReLU whose saved output, or pre-activation, is `act`).  The input size H x W is a parameter: a stride-2
 // output size does not determine it.  Every element of dx is written exactly once.
-#include "sg3_igemm_f32.h"
+#include "sg3_conv2d_plan.h"
 
 namespace sg3 {
 
@@ -183,35 +183,31 @@ conv2d_dgrad_kernel(DgradParams p) {
 }
 
 template <int KS, int STRIDE, int WM, int WN, int TM, int TN>
-static int launch_dgrad(const sg3_conv2d_dgrad_params& q, hipStream_t st) {
-    constexpr int BM = WM * TM * 32, ROWS = WN * TN, KC = ConvK<KS>::KC;
+static int launch_dgrad(const sg3_conv2d_dgrad_params& q, const Conv2dPlan& pl, hipStream_t st) {
     DgradParams p;
     p.dy = q.dy; p.wp = q.wPacked; p.dx = q.dx; p.act = q.act; p.slope = q.slope; p.addend = q.addend;
     for (int d = 0; d < 4; d++) p.addStride[d] = q.addStride[d];
     p.N = q.N; p.I = q.I; p.O = q.O; p.H = q.H; p.W = q.W; p.OH = q.OH; p.OW = q.OW; p.pad = KS / 2;
-    p.nch = ceil_div(q.O, KC);
-    p.xTiles = ceil_div(ceil_div(q.W, STRIDE), 32); p.yTiles = ceil_div(ceil_div(q.H, STRIDE), ROWS); p.mTiles = ceil_div(q.I, BM);
-    const long long total = (long long)p.xTiles * p.yTiles * p.mTiles * q.N * STRIDE * STRIDE;
-    if (total > 0x7fffffffLL) { set_error("conv2d_dgrad: grid too large"); return SG3_BAD_ARG; }
-    p.totalBlocks = (int)total;
-    hipLaunchKernelGGL((conv2d_dgrad_kernel<KS, STRIDE, WM, WN, TM, TN>), dim3((unsigned)total), dim3(256), 0, st, p);
+    p.nch = pl.nch; p.xTiles = pl.xTiles; p.yTiles = pl.yTiles; p.mTiles = pl.mTiles; p.totalBlocks = pl.totalBlocks;
+    hipLaunchKernelGGL((conv2d_dgrad_kernel<KS, STRIDE, WM, WN, TM, TN>), dim3((unsigned)pl.totalBlocks), dim3(pl.block), 0, st, p);
     SG3_LAUNCH_CHECK("conv2d_dgrad_kernel");
     return SG3_OK;
 }
 
-// 64 channels x (2 rows x 32 columns) of one class per workgroup; the stem (3 input channels) takes 32 x (4 rows x 32)
+// plan coordinates -> template instantiation: the two tiles per (KS, STRIDE)
 template <int KS, int STRIDE>
-static int dispatch_dgrad(const sg3_conv2d_dgrad_params& q, hipStream_t st) {
-    if (q.I > 32) return launch_dgrad<KS, STRIDE, 2, 2, 1, 1>(q, st);
-    return launch_dgrad<KS, STRIDE, 1, 4, 1, 1>(q, st);
+static int launch_tile(const sg3_conv2d_dgrad_params& q, const Conv2dPlan& pl, hipStream_t st) {
+    return pl.WM == 2 ? launch_dgrad<KS, STRIDE, 2, 2, 1, 1>(q, pl, st) : launch_dgrad<KS, STRIDE, 1, 4, 1, 1>(q, pl, st);
 }
 
 } // namespace sg3
 
 extern "C" {
 
-int sg3_conv2d_dgrad(const sg3_conv2d_dgrad_params* p, void* stream) {
+// the checks and the plan of the launch
+int sg3_conv2d_dgrad_dispatch(const sg3_conv2d_dgrad_params* p, sg3_conv2d_dispatch_info* out) {
     using namespace sg3;
+    SG3_REQUIRE(out, "conv2d_dgrad_dispatch: null argument");
     SG3_REQUIRE(p && p->dy && p->wPacked && p->dx, "conv2d_dgrad: null tensor");
     SG3_REQUIRE(p->N > 0 && p->I > 0 && p->O > 0 && p->H > 0 && p->W > 0, "conv2d_dgrad: empty tensor");
     SG3_REQUIRE(p->k == 1 || p->k == 3, "conv2d_dgrad: kernel size must be 1 or 3");
@@ -220,9 +216,19 @@ int sg3_conv2d_dgrad(const sg3_conv2d_dgrad_params* p, void* stream) {
                 "conv2d_dgrad: dy is %d x %d, but a %d x %d input with k %d, stride %d, padding k / 2 gives another size", p->OH, p->OW, p->H, p->W, p->k, p->stride);
     SG3_REQUIRE(!p->act || p->slope, "conv2d_dgrad: slope missing");
     SG3_REQUIRE((long long)p->N * p->I * p->H * p->W < 0x7fffffffLL && (long long)p->N * p->O * p->OH * p->OW < 0x7fffffffLL, "conv2d_dgrad: tensor too large");
+    *out = plan_conv2d_dgrad(*p);
+    SG3_REQUIRE(out->totalBlocks > 0, "conv2d_dgrad: grid too large");
+    return SG3_OK;
+}
+
+int sg3_conv2d_dgrad(const sg3_conv2d_dgrad_params* p, void* stream) {
+    using namespace sg3;
+    Conv2dPlan pl;
+    const int rc = sg3_conv2d_dgrad_dispatch(p, &pl);
+    if (rc != SG3_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (p->k == 3) return p->stride == 1 ? dispatch_dgrad<3, 1>(*p, st) : dispatch_dgrad<3, 2>(*p, st);
-    return p->stride == 1 ? dispatch_dgrad<1, 1>(*p, st) : dispatch_dgrad<1, 2>(*p, st);
+    if (p->k == 3) return p->stride == 1 ? launch_tile<3, 1>(*p, pl, st) : launch_tile<3, 2>(*p, pl, st);
+    return p->stride == 1 ? launch_tile<1, 1>(*p, pl, st) : launch_tile<1, 2>(*p, pl, st);
 }
 
 } // extern "C"

@@ -16,31 +16,9 @@
 // K is split over nSplit workgroup sets (sg3_conv2d_wgrad_sum_splits: host only, the same for every device so that results do not
 // depend on the machine); each set writes its own partial [O][I][k][k] and a second small launch adds the partials in split order.
 // No atomics anywhere: bit-identical on repeat.
-#include "sg3_igemm_f32.h"
+#include "sg3_conv2d_plan.h"
 
 namespace sg3 {
-
-// output pixels per K chunk: 32 at stride 1, 16 at stride 2 (the staged input patch is then 34 / 33 columns wide either way)
-__host__ __device__ constexpr int ws_px(int stride) { return 32 / stride; }
-constexpr int WS_TILE = 64;         // output / input channels per workgroup
-constexpr int WS_BLOCKS = 512;      // workgroups the planner aims for (two per CU of an MI355X)
-
-struct WgradSumPlan { int OH, OW, xSegs, nChunks, nSplit, chunksPerSplit, oTiles, iTiles; };
-
-static bool wgrad_sum_plan(int N, int I, int O, int H, int W, int k, int stride, WgradSumPlan* pl) {
-    const int pad = k / 2;
-    pl->OH = (H + 2 * pad - k) / stride + 1; pl->OW = (W + 2 * pad - k) / stride + 1;
-    pl->xSegs = ceil_div(pl->OW, ws_px(stride));
-    const long long chunks = (long long)N * pl->OH * pl->xSegs;
-    if (chunks <= 0 || chunks > 0x7fffffffLL) return false;
-    pl->nChunks = (int)chunks;
-    pl->oTiles = ceil_div(O, WS_TILE); pl->iTiles = ceil_div(I, WS_TILE);
-    const long long tiles = (long long)pl->oTiles * pl->iTiles;
-    long long want = WS_BLOCKS / tiles; if (want < 1) want = 1; if (want > chunks) want = chunks;
-    pl->chunksPerSplit = (int)ceil_div64(chunks, want);
-    pl->nSplit = ceil_div(pl->nChunks, pl->chunksPerSplit);          // no empty split
-    return true;
-}
 
 struct WgradSumParams {
     const float* x; const float* dy; float* out; const float* inScale; const float* inShift;
@@ -164,19 +142,16 @@ conv2d_wgrad_sum_reduce_kernel(const float* partial, float* dw, int total, int n
 }
 
 template <int KS, int STRIDE>
-static int launch_wgrad_sum(const sg3_conv2d_wgrad_sum_params& q, const WgradSumPlan& pl, hipStream_t st) {
+static int launch_wgrad_sum(const sg3_conv2d_wgrad_sum_params& q, const Conv2dPlan& pl, hipStream_t st) {
     WgradSumParams p;
     p.x = q.x; p.dy = q.dy; p.inScale = q.inScale; p.inShift = q.inShift;
     p.out = pl.nSplit > 1 ? q.partial : q.dw;
-    p.N = q.N; p.I = q.I; p.O = q.O; p.H = q.H; p.W = q.W; p.OH = pl.OH; p.OW = pl.OW; p.pad = KS / 2;
+    p.N = q.N; p.I = q.I; p.O = q.O; p.H = q.H; p.W = q.W; p.OH = pl.outH; p.OW = pl.outW; p.pad = KS / 2;
     p.xSegs = pl.xSegs; p.nChunks = pl.nChunks; p.chunksPerSplit = pl.chunksPerSplit; p.oTiles = pl.oTiles; p.iTiles = pl.iTiles;
-    const long long blocks = (long long)pl.oTiles * pl.iTiles * pl.nSplit;
-    if (blocks > 0x7fffffffLL) { set_error("conv2d_wgrad_sum: grid too large"); return SG3_BAD_ARG; }
-    hipLaunchKernelGGL((conv2d_wgrad_sum_kernel<KS, STRIDE>), dim3((unsigned)blocks), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((conv2d_wgrad_sum_kernel<KS, STRIDE>), dim3((unsigned)pl.totalBlocks), dim3(pl.block), 0, st, p);
     SG3_LAUNCH_CHECK("conv2d_wgrad_sum_kernel");
     if (pl.nSplit > 1) {
-        const int total = q.O * q.I * KS * KS;
-        hipLaunchKernelGGL(conv2d_wgrad_sum_reduce_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, st, q.partial, q.dw, total, pl.nSplit);
+        hipLaunchKernelGGL(conv2d_wgrad_sum_reduce_kernel, dim3((unsigned)pl.reduceGrid), dim3(256), 0, st, q.partial, q.dw, q.O * q.I * KS * KS, pl.nSplit);
         SG3_LAUNCH_CHECK("conv2d_wgrad_sum_reduce_kernel");
     }
     return SG3_OK;
@@ -186,12 +161,30 @@ static int launch_wgrad_sum(const sg3_conv2d_wgrad_sum_params& q, const WgradSum
 
 extern "C" {
 
-int sg3_conv2d_wgrad_sum_splits(int N, int I, int O, int H, int W, int k, int stride, int* nSplit, int* chunksPerSplit, int* xSegs) {
+// the checks and the plan of the launch
+int sg3_conv2d_wgrad_sum_dispatch(const sg3_conv2d_wgrad_sum_params* p, sg3_conv2d_dispatch_info* out) {
     using namespace sg3;
-    SG3_REQUIRE(N > 0 && I > 0 && O > 0 && H > 0 && W > 0, "conv2d_wgrad_sum_splits: empty tensor");
-    SG3_REQUIRE((k == 1 || k == 3) && (stride == 1 || stride == 2), "conv2d_wgrad_sum_splits: kernel size 1 or 3, stride 1 or 2");
-    WgradSumPlan pl;
-    SG3_REQUIRE(wgrad_sum_plan(N, I, O, H, W, k, stride, &pl), "conv2d_wgrad_sum_splits: too many pixels");
+    SG3_REQUIRE(out, "conv2d_wgrad_sum_dispatch: null argument");
+    SG3_REQUIRE(p && p->x && p->dy && p->dw, "conv2d_wgrad_sum: null tensor");
+    SG3_REQUIRE(p->N > 0 && p->I > 0 && p->O > 0 && p->H > 0 && p->W > 0, "conv2d_wgrad_sum: empty tensor");
+    SG3_REQUIRE(p->k == 1 || p->k == 3, "conv2d_wgrad_sum: kernel size must be 1 or 3");
+    SG3_REQUIRE(p->stride == 1 || p->stride == 2, "conv2d_wgrad_sum: stride must be 1 or 2");
+    SG3_REQUIRE((p->inScale == nullptr) == (p->inShift == nullptr), "conv2d_wgrad_sum: inScale and inShift come together");
+    *out = plan_conv2d_wgrad_sum(*p);
+    SG3_REQUIRE(out->nChunks > 0, "conv2d_wgrad_sum: too many pixels");
+    SG3_REQUIRE(out->nSplit == 1 || p->partial, "conv2d_wgrad_sum: %d splits need the partial scratch", out->nSplit);
+    SG3_REQUIRE((long long)p->N * p->I * p->H * p->W < 0x7fffffffLL && (long long)p->N * p->O * out->outH * out->outW < 0x7fffffffLL &&
+                (long long)out->nSplit * p->O * p->I * p->k * p->k < 0x7fffffffLL, "conv2d_wgrad_sum: tensor too large");
+    SG3_REQUIRE(out->totalBlocks > 0, "conv2d_wgrad_sum: grid too large");
+    return SG3_OK;
+}
+
+int sg3_conv2d_wgrad_sum_splits(int N, int I, int O, int H, int W, int k, int stride, int* nSplit, int* chunksPerSplit, int* xSegs) {
+    float* const set = reinterpret_cast<float*>(16);          // the checks read pointers for presence only
+    sg3_conv2d_wgrad_sum_params q = {set, set, nullptr, nullptr, set, set, N, I, O, H, W, k, stride};
+    sg3::Conv2dPlan pl;
+    const int rc = sg3_conv2d_wgrad_sum_dispatch(&q, &pl);
+    if (rc != SG3_OK) return rc;
     if (nSplit) *nSplit = pl.nSplit;
     if (chunksPerSplit) *chunksPerSplit = pl.chunksPerSplit;
     if (xSegs) *xSegs = pl.xSegs;
@@ -200,16 +193,9 @@ int sg3_conv2d_wgrad_sum_splits(int N, int I, int O, int H, int W, int k, int st
 
 int sg3_conv2d_wgrad_sum(const sg3_conv2d_wgrad_sum_params* p, void* stream) {
     using namespace sg3;
-    SG3_REQUIRE(p && p->x && p->dy && p->dw, "conv2d_wgrad_sum: null tensor");
-    SG3_REQUIRE(p->N > 0 && p->I > 0 && p->O > 0 && p->H > 0 && p->W > 0, "conv2d_wgrad_sum: empty tensor");
-    SG3_REQUIRE(p->k == 1 || p->k == 3, "conv2d_wgrad_sum: kernel size must be 1 or 3");
-    SG3_REQUIRE(p->stride == 1 || p->stride == 2, "conv2d_wgrad_sum: stride must be 1 or 2");
-    SG3_REQUIRE((p->inScale == nullptr) == (p->inShift == nullptr), "conv2d_wgrad_sum: inScale and inShift come together");
-    WgradSumPlan pl;
-    SG3_REQUIRE(wgrad_sum_plan(p->N, p->I, p->O, p->H, p->W, p->k, p->stride, &pl), "conv2d_wgrad_sum: too many pixels");
-    SG3_REQUIRE(pl.nSplit == 1 || p->partial, "conv2d_wgrad_sum: %d splits need the partial scratch", pl.nSplit);
-    SG3_REQUIRE((long long)p->N * p->I * p->H * p->W < 0x7fffffffLL && (long long)p->N * p->O * pl.OH * pl.OW < 0x7fffffffLL &&
-                (long long)pl.nSplit * p->O * p->I * p->k * p->k < 0x7fffffffLL, "conv2d_wgrad_sum: tensor too large");
+    Conv2dPlan pl;
+    const int rc = sg3_conv2d_wgrad_sum_dispatch(p, &pl);
+    if (rc != SG3_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (p->k == 3) return p->stride == 1 ? launch_wgrad_sum<3, 1>(*p, pl, st) : launch_wgrad_sum<3, 2>(*p, pl, st);
     return p->stride == 1 ? launch_wgrad_sum<1, 1>(*p, pl, st) : launch_wgrad_sum<1, 2>(*p, pl, st);

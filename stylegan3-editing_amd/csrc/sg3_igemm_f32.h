@@ -1,7 +1,8 @@
 // sg3_igemm_f32.h -- what the MFMA implicit-GEMM convolution kernels (sg3_modconv.hip, sg3_conv2d.hip, sg3_conv2d_dgrad.hip) share
 // on the device: the vector types, the K chunk of the packed fp32 weights, the XCD block renumbering and the C-layout row of an
 // accumulator register.  The exact-fp32 main loop itself (modconv_mfma_kernel, conv2d_mfma_kernel, conv2d_dgrad_kernel) is NOT
-// here: each kernel keeps its own copy, see DESIGN.md 3.3.1.
+// here: each kernel keeps its own copy, see DESIGN.md 3.3.1.  The host-side plan of the encoder convolutions (sg3_conv2d_plan.h) takes
+// ConvK from here.
 #pragma once
 #include "sg3_common.h"
 

@@ -19,6 +19,7 @@ SG3_CONV_FP32, SG3_CONV_F16X3, SG3_CONV_F16, SG3_CONV_F16X3_F23, SG3_CONV_F16_F2
 SG3_MODCONV_FP32_MFMA, SG3_MODCONV_TORGB, SG3_MODCONV_ROWS, SG3_MODCONV_FLAT, SG3_MODCONV_GEMM1, SG3_MODCONV_F23 = range(6)   # sg3_modconv_dispatch_info.family
 SG3_FLRELU_NONE, SG3_FLRELU_POINTWISE, SG3_FLRELU_STREAM = range(3)                             # sg3_filtered_lrelu_dispatch_info.kind
 SG3_CONV2D_FORM_F16X3 = 16          # sg3_conv2d_form: first f16x3 form (include/sg3_ops.h)
+SG3_CONV2D_FP32_MFMA, SG3_CONV2D_F16X3, SG3_CONV2D_DGRAD, SG3_CONV2D_WGRAD_SUM = range(4)       # sg3_conv2d_dispatch_info.family
 _DTYPE = {torch.float32: SG3_F32, torch.float16: SG3_F16, torch.float64: SG3_F64}
 
 c_i32, c_i64, c_f32, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
@@ -262,6 +263,15 @@ class Conv2dWgradSumParams(ctypes.Structure):
                 ('N', c_i32), ('I', c_i32), ('O', c_i32), ('H', c_i32), ('W', c_i32), ('k', c_i32), ('stride', c_i32)]
 
 
+class Conv2dDispatchInfo(ctypes.Structure):
+    _fields_ = [(n, c_i32) for n in ('family', 'form', 'KS', 'STRIDE', 'WM', 'WN', 'TM', 'TN', 'CHAINS', 'kc', 'nch', 'outH', 'outW', 'xTiles', 'yTiles',
+                                     'mTiles', 'classes', 'xSegs', 'nChunks', 'nSplit', 'chunksPerSplit', 'oTiles', 'iTiles', 'reduceGrid', 'totalBlocks',
+                                     'block', 'ldsBytes')]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class BnTrainStatsParams(ctypes.Structure):
     _fields_ = [('x', c_vp), ('gamma', c_vp), ('beta', c_vp), ('partial', c_vp), ('mean', c_vp), ('meanLo', c_vp), ('var', c_vp), ('invstd', c_vp), ('a', c_vp), ('b', c_vp),
                 ('N', c_i32), ('C', c_i32), ('H', c_i32), ('W', c_i32), ('eps', c_f32)]
@@ -356,6 +366,9 @@ EXPORTS = [
     ('sg3_lpips_head', ctypes.c_int, [ctypes.POINTER(LpipsHeadParams), c_vp]),
     ('sg3_conv2d_wgrad_sum_splits', ctypes.c_int, [ctypes.c_int] * 7 + [ctypes.POINTER(ctypes.c_int)] * 3),
     ('sg3_conv2d_wgrad_sum', ctypes.c_int, [ctypes.POINTER(Conv2dWgradSumParams), c_vp]),
+    ('sg3_conv2d_dispatch', ctypes.c_int, [ctypes.POINTER(Conv2dParams), ctypes.c_int, ctypes.POINTER(Conv2dDispatchInfo)]),
+    ('sg3_conv2d_dgrad_dispatch', ctypes.c_int, [ctypes.POINTER(Conv2dDgradParams), ctypes.POINTER(Conv2dDispatchInfo)]),
+    ('sg3_conv2d_wgrad_sum_dispatch', ctypes.c_int, [ctypes.POINTER(Conv2dWgradSumParams), ctypes.POINTER(Conv2dDispatchInfo)]),
     ('sg3_bn_train_partials', ctypes.c_int, [ctypes.c_int] * 3),
     ('sg3_bn_train_stats', ctypes.c_int, [ctypes.POINTER(BnTrainStatsParams), c_vp]),
     ('sg3_bn_train_apply', ctypes.c_int, [ctypes.POINTER(BnTrainApplyParams), c_vp]),

@@ -6,9 +6,12 @@ import torch
 import torch.nn.functional as F
 
 # (k, stride, I, O, H, W): every (k, stride) form, channel counts that are no multiple of the 64 x 64 tile (and one above it), rows
-# wider than one 32- (stride 1) or 16-pixel (stride 2) chunk with a ragged last chunk, maps smaller than one chunk
+# wider than one 32- (stride 1) or 16-pixel (stride 2) chunk with a ragged last chunk, maps smaller than one chunk; then, per
+# (k, stride), more than 256 (o, i) tiles: the planner gives those ONE split (no partials, no reduce launch), which a batch of two
+# samples reaches in no other way (tests/test_conv2d_dispatch_cpu.py checks which kernels and how many splits this list reaches)
 WGRAD_SHAPES = [(3, 1, 64, 64, 9, 13), (3, 1, 6, 64, 12, 12), (3, 1, 40, 20, 5, 70), (3, 2, 64, 64, 13, 9), (3, 2, 128, 128, 7, 7),
-                (3, 2, 40, 20, 7, 131), (1, 2, 64, 128, 13, 9), (1, 2, 70, 20, 6, 67), (1, 1, 40, 20, 5, 70), (3, 2, 3, 20, 7, 35)]
+                (3, 2, 40, 20, 7, 131), (1, 2, 64, 128, 13, 9), (1, 2, 70, 20, 6, 67), (1, 1, 40, 20, 5, 70), (3, 2, 3, 20, 7, 35),
+                (3, 1, 1, 16448, 1, 12), (3, 2, 1, 16448, 1, 24), (1, 1, 1, 16448, 1, 12), (1, 2, 1, 16448, 1, 24)]
 
 
 def out_hw(h, w, k, stride):

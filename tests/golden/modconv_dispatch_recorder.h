@@ -2,7 +2,9 @@
 // record what their host side WOULD launch, without a GPU: the launch macro, the dynamic-LDS attribute call and the device
 // queries are replaced after <hip/hip_runtime.h> has declared the real ones.  Used once per change of the dispatch to regenerate
 // tests/golden/modconv_dispatch.json (see make_modconv_dispatch.py); never part of the product library.  csrc/sg3_filtered_lrelu.hip
-// is recorded the same way for tests/golden/flrelu_dispatch.json (make_flrelu_dispatch.py, flrelu_dispatch_recorder.cpp).
+// is recorded the same way for tests/golden/flrelu_dispatch.json (make_flrelu_dispatch.py, flrelu_dispatch_recorder.cpp), and
+// csrc/sg3_conv2d.hip, sg3_conv2d_dgrad.hip and sg3_conv2d_wgrad_sum.hip for tests/golden/conv2d_dispatch.json
+// (make_conv2d_dispatch.py, conv2d_dispatch_recorder.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cxxabi.h>
@@ -10,6 +12,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <string>
+#include <type_traits>
+#include <utility>
 
 namespace rec {
 
@@ -29,10 +33,24 @@ inline std::string kernel_name(const void* f) {
     return s;
 }
 
-// tile geometry of the parameter block a convolution kernel takes (ConvParams / F23Params); other first arguments have none
+template <class P, class = void> struct has_out_pitch : std::false_type {};
+template <class P> struct has_out_pitch<P, decltype((void)std::declval<const P&>().outPitch)> : std::true_type {};
+
+// tile geometry of the parameter block a convolution kernel takes (ConvParams / F23Params with a row pitch; PlainConvParams /
+// DgradParams of the encoder convolutions with the block count); other first arguments have none
 template <class P> auto geometry(const P& p, int) -> decltype((void)p.xTiles, std::string()) {
-    char b[160];
-    snprintf(b, sizeof b, ",\"nch\":%d,\"xTiles\":%d,\"yTiles\":%d,\"mTiles\":%d,\"outPitch\":%d", p.nch, p.xTiles, p.yTiles, p.mTiles, p.outPitch);
+    char b[200];
+    if constexpr (has_out_pitch<P>::value)
+        snprintf(b, sizeof b, ",\"nch\":%d,\"xTiles\":%d,\"yTiles\":%d,\"mTiles\":%d,\"outPitch\":%d", p.nch, p.xTiles, p.yTiles, p.mTiles, p.outPitch);
+    else
+        snprintf(b, sizeof b, ",\"nch\":%d,\"xTiles\":%d,\"yTiles\":%d,\"mTiles\":%d,\"totalBlocks\":%d", p.nch, p.xTiles, p.yTiles, p.mTiles, p.totalBlocks);
+    return b;
+}
+// K decomposition of the parameter block the batch-summed weight gradient takes (WgradSumParams)
+template <class P> auto geometry(const P& p, int) -> decltype((void)p.chunksPerSplit, std::string()) {
+    char b[200];
+    snprintf(b, sizeof b, ",\"OH\":%d,\"OW\":%d,\"xSegs\":%d,\"nChunks\":%d,\"chunksPerSplit\":%d,\"oTiles\":%d,\"iTiles\":%d",
+             p.OH, p.OW, p.xSegs, p.nChunks, p.chunksPerSplit, p.oTiles, p.iTiles);
     return b;
 }
 // work decomposition of the parameter block the filtered_lrelu streaming kernel takes (StreamParams)

@@ -76,7 +76,8 @@ def test_face_pool_forward_and_adjoint_against_fp64(H):
 DGRAD_SHAPES = [(3, 2, 64, 64, 13, 9), (3, 2, 64, 64, 20, 24), (3, 2, 128, 128, 7, 7), (3, 2, 128, 128, 14, 14),
                 (1, 2, 64, 128, 13, 9), (1, 2, 64, 128, 20, 24), (3, 1, 64, 64, 9, 13), (3, 1, 3, 64, 12, 12),
                 (3, 1, 40, 20, 5, 70), (3, 2, 40, 20, 7, 131), (1, 1, 40, 20, 5, 70), (1, 2, 70, 20, 6, 67),
-                # the 32-channel tile (I <= 32) of the other three (k, stride): two x tiles, a ragged last chunk, unequal parity classes
+                # two x tiles, a ragged last chunk, unequal parity classes.  That the list reaches all eight kernels (two tiles per
+                # (k, stride)) is checked without a GPU: tests/test_conv2d_dispatch_cpu.py::test_gpu_case_lists_reach_every_kernel
                 (3, 2, 3, 20, 7, 35), (1, 1, 3, 20, 5, 35), (1, 2, 3, 20, 6, 35)]
 GUARD = 4096
 SENTINEL = 777.0
