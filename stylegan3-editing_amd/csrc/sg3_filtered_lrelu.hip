@@ -29,21 +29,25 @@
 //   Lane fill (plain forward): planes at most 54 columns wide run TWO per wave (template G = 2: lanes 0-31 / 32-63, own LDS
 //   segments, own bias and gain); rows of 120 n + (1..54) columns are cut into n full strips, one plane per wave, plus the
 //   remainder strip with two planes per wave -- in one launch of the G = 2 kernel (StreamParams.wideBlocks) where that costs
-//   no occupancy, in two launches otherwise (`launch_stream`).
+//   no occupancy, in two launches otherwise (`launch_stream`, sg3_flrelu_host.hip).
 //
-// Supported by the streaming kernel (`stream_supported` / `stream_params_ok` below are the authority): fp32 / fp16 I/O with
+// Supported by the streaming kernel (`stream_supported` / `stream_params_ok`, sg3_flrelu_plan.h, are the authority): fp32 / fp16 I/O with
 // unit innermost stride, slope in [0,1], and
 //   forward, plain or sign-writing (training):  up 2 (12 taps) | up 4 (24 taps), separable;  down 2 with a separable 12-tap
 //       filter (config T, and the critically sampled layers of config R) or a full 12x12 filter (radial layers of config R;
 //       RADIAL 1|2, or 5|6 when the caller promises mirror-symmetric rows);
 //   adjoint (sign-reading):  up 2 with a separable 12-tap filter or a full 12x12 filter (RADIAL 3|4: the radial layers' down
 //       filter ends up on the up side), down 2 (12 taps) | down 4 (24 taps), separable.
-// `flrelu_pointwise_kernel` covers up = down = 1 with 1x1 filters (the ToRGB layer).  Anything else returns SG3_NO_KERNEL and
-// the caller composes upfirdn2d + filtered_lrelu_act + upfirdn2d, exactly like the reference's rc = -1 path.
+// `flrelu_pointwise_kernel` (sg3_flrelu_host.hip) covers up = down = 1 with 1x1 filters (the ToRGB layer).  Anything else returns
+// SG3_NO_KERNEL and the caller composes upfirdn2d + filtered_lrelu_act + upfirdn2d, exactly like the reference's rc = -1 path.
 //
 // Algorithmic traffic: C*(xH*xW + yH*yW)*sizeof(T) bytes per image -- the roofline figure bench.py uses.
-#include "sg3_flrelu_plan.h"
-#include <atomic>
+//
+// This file is the DEVICE side alone: the kernel template, and at its end the table of instantiations with the lookup that hands
+// their addresses to the host side (sg3_flrelu_host.hip: launchers, the small kernels, the C entry points).  The table is cut into
+// parts, -DSG3_FLRELU_PART=k compiles one of them, and the library is linked from all of them (csrc/Makefile); without the macro the
+// file holds every kernel.  bench.py and tests/test_tools_cpu.py tie profiles/flrelu_traffic*.json to the sha256 of this file.
+#include "sg3_flrelu_kernels.h"
 #include <utility>
 
 // rows of input the streaming kernel keeps in flight per wave (each costs NL registers per lane): three rows are ~3 x 1.5 us
@@ -64,37 +68,6 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) float lds_f;          // explicit LDS address space: keeps ds_* instructions
 typedef __attribute__((address_space(3))) v2f lds_v2f;
 typedef __attribute__((address_space(3))) v4f lds_v4f;
-
-struct StreamParams {
-    const void* x; void* y; const void* b; const float* fu; const float* fd;
-    int C, xH, xW, yH, yW;
-    int planes;                    // N * C
-    long long xsN, xsC, xsH;      // element strides (innermost stride is 1)
-    long long ysN, ysC, ysH;
-    long long bStride;
-    int px0, py0;
-    int TW;                        // output columns per strip (<= 122)
-    int ox0Base;                   // first output column of strip 0 (one-plane blocks) / of the packed strip (two-plane blocks)
-    int wideBlocks;                // G = 2 kernels: the first wideBlocks (logical) blocks work on ONE plane each, strips of TW columns
-                                   // from column 0; the others on two planes, columns ox0Base .. yW - 1
-    int CH;                        // output rows per chunk
-    int nStrips, nChunks;
-    int totalBlocks;
-    float gain, slope, clamp;
-    int flip;
-    int fastAct;                   // plain forward: 1 = try the one-instruction activation first (see `fast_threshold`), 0 = never
-    float* ysum;                   // optional [N*C][nChunks*nStrips]: sum of this block's outputs (adjoint passes only: their bias gradient)
-    float* ymax;                   // optional, same shape: max |output| of this block (adjoint passes only: the operand bound of the
-                                   // convolution gradients that read the result next)
-    unsigned char* s;              // sign tensor [N*C][sH][sWb] (2 bits per upsampled sample, 4 per byte), or null
-    int sH, sWb, sx, sy;           // rows, bytes per row, offset of the upsampled buffer inside the sign tensor
-#ifdef SG3_STAMPS
-    unsigned long long* stamps;    // diagnostic build (tools/flrelu_clock.hip): per block {shader cycles, 100 MHz ticks} of the wave's life
-#endif
-};
-#ifdef SG3_STAMPS
-static unsigned long long* g_stamps = nullptr;
-#endif
 
 __device__ __forceinline__ int to_sgpr_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ float to_sgpr(float v) {
@@ -247,6 +220,7 @@ __device__ __forceinline__ v2f up2d_pair(const TapRow& t, int s) {
     return (j & 1) ? (v2f){v.z, v.w} : (v2f){v.x, v.y};
 }
 
+// StreamParams, the kernel's parameter block, and `fast_threshold`: sg3_flrelu_kernels.h (the host side fills / calls them too)
 // StreamCfg<U, D>, the tile constants of the streaming kernel: sg3_flrelu_plan.h (the launch plan reads MAXTW and PACKTW)
 
 // element <-> fp32 through raw buffer instructions: the hardware range check (offset >= num_records reads 0 /
@@ -298,25 +272,6 @@ struct WaveState {
     int inBase, outBase;          // packed mode: this lane's window start in the input LDS row / its 4 samples' place in the output LDS row
     int ooff[2];                  // packed mode: byte offsets of this lane's two output columns from the first plane's row (out of range: none)
 };
-
-// Threshold of the one-instruction activation (plain forward).  The kernel forms every upsampled sample u from staged samples x
-// (input + bias) through one phase of the separable up filter per direction, taps scaled by `up`: |u| <= hv * max |x| with
-// hv = (up * max over phases of sum |f|)^2 (the phases map onto each other under flip).  For max |x| <= T, slope |u| <= clamp / gain
-// holds -- with a 1e-4 margin over the rounding of the sums, of T and of u -- and |u| stays far below overflow.  -1: no fast path.
-// Host and device run this same code (sg3_filtered_lrelu_fast_threshold exposes it to the CPU tests).
-__host__ __device__ static inline float fast_threshold(const float* fu, int taps, int up, float gain, float slope, float clamp) {
-    const float clampv = clamp / gain;                 // as the kernel forms it
-    if (!(clampv > 0.f)) return -1.f;
-    float hs = 0.f;
-    for (int ph = 0; ph < up; ph++) {
-        float s = 0.f;
-        for (int k = ph; k < taps; k += up) s += fabsf(fu[k]);
-        hs = fmaxf(hs, s);
-    }
-    hs *= (float)up;
-    const float hv = hs * hs;
-    return fminf(clampv / (slope * hv), 0x1p124f / fmaxf(hv, 1.f)) * 0.9999f;
-}
 
 // SIGNS: 0 = plain forward; 1 = forward that also writes the sign tensor (training); 2 = adjoint pass: the stored signs
 // replace the nonlinearity (gradient of lrelu + clamp).
@@ -995,265 +950,95 @@ flrelu_stream_kernel(StreamParams p) {
 }
 
 // ---------------------------------------------------------------------------
-// up = down = 1, 1x1 filters: y = clamp(lrelu((x + b) * fu * gain)) * fd   (ToRGB layer: clamp(x + b))
-struct PointParams {
-    const void* x; void* y; const void* b;
-    const float* fu; const float* fd;
-    int N, C, H, W;
-    long long xs[4], ys[4], bStride;
-    int px0, py0, yH, yW;
-    float gain, slope, clamp;
-};
-
-template <typename T>
-__global__ void __launch_bounds__(256)
-flrelu_pointwise_kernel(PointParams p) {
-    const float fu = p.fu[0], fd = p.fd[0];
-    const long long total = (long long)p.N * p.C * p.yH * p.yW;
-    const long long gs = (long long)gridDim.x * blockDim.x;
-    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gs) {
-        const int ox = (int)(idx % p.yW); long long t = idx / p.yW;
-        const int oy = (int)(t % p.yH); t /= p.yH;
-        const int c = (int)(t % p.C); const int n = (int)(t / p.C);
-        const int ix = ox - p.px0, iy = oy - p.py0;
-        float v = 0.f;
-        if ((unsigned)ix < (unsigned)p.W && (unsigned)iy < (unsigned)p.H)
-            v = io<T>::ld((const T*)p.x + n * p.xs[0] + c * p.xs[1] + iy * p.xs[2] + ix * p.xs[3]) + (p.b ? io<T>::ld((const T*)p.b + c * p.bStride) : 0.f);
-        v *= fu * p.gain;
-        v = v < 0.f ? v * p.slope : v;
-        v = fminf(fmaxf(v, -p.clamp), p.clamp);
-        io<T>::st((T*)p.y + n * p.ys[0] + c * p.ys[1] + oy * p.ys[2] + ox * p.ys[3], v * fd);
-    }
-}
-
-// ---------------------------------------------------------------------------
-// Which kernel, how many launches and what grid a call takes: plan_filtered_lrelu, sg3_flrelu_plan.h.
-//
-// The up-4 separable plain forward has two forms that compute the same thing bit for bit: the default (up taps placed by hand, at
-// most 128 VGPRs, four waves per SIMD) and the earlier one (`Stream`'s WIDE).  A process setting, seeded ONCE from the environment
-// (SG3_FLRELU_UP4_WIDE=1: A/B timing) and changed only by an explicit sg3_filtered_lrelu_force_up4_wide call (the bit-identity test).
-static std::atomic<int> g_up4_wide{[] { const char* e = getenv("SG3_FLRELU_UP4_WIDE"); return (e && e[0] == '1') ? 1 : 0; }()};
-
-// The per-workgroup partial sums / maxima an adjoint launch left ([N][C][slots] each) -> the bias gradient db[c] = sum over (n, slot)
-// and max |dx| = max over everything, in one small launch (as torch ops: a strided reduction and a max, ~19 us per layer and PTI step).
-// One block: thread per channel, (n, slot) walked in order -- a fixed summation order, so db is reproducible.
-__global__ void __launch_bounds__(256)
-flrelu_finish_partials_kernel(const float* __restrict__ psum, const float* __restrict__ pmax, int N, int C, int slots,
-                              float* __restrict__ db, float* __restrict__ amax) {
-    __shared__ float red[4];
-    float mx = 0.f;
-    for (int c = threadIdx.x; c < C; c += 256) {
-        float s = 0.f;
-        for (int n = 0; n < N; n++) {
-            const size_t base = ((size_t)n * C + c) * slots;
-            for (int k = 0; k < slots; k++) {
-                s += psum[base + k];
-                if (pmax) mx = __builtin_fmaxf(mx, pmax[base + k]);
-            }
-        }
-        db[c] = s;
-    }
-    if (!amax) return;
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) mx = __builtin_fmaxf(mx, __shfl_xor(mx, m));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) amax[0] = __builtin_fmaxf(__builtin_fmaxf(red[0], red[1]), __builtin_fmaxf(red[2], red[3]));
-}
-
-typedef void (*StreamKernel)(StreamParams);
-
-// The kernel of one plan entry: the 82 instantiations per tensor type, nullptr for coordinates none of them has.
+// The kernel of one plan entry.  This is where the kernels' addresses are taken, so this is where they are instantiated.
 template <typename T, int U, int D, int R, int S, int G, int W, int... V>
 static StreamKernel stream_kernel_vph(int vph, std::integer_sequence<int, V...>) {
     StreamKernel f = nullptr;
     ((vph == V ? (void)(f = flrelu_stream_kernel<T, U, D, V, R, S, G, W>) : (void)0), ...);
     return f;
 }
-template <typename T, int U, int D, int S, int G, class VS, int... R>
-static StreamKernel stream_kernel_radial(int radial, int vph, VS vs, std::integer_sequence<int, R...>) {
-    StreamKernel f = nullptr;
-    ((radial == R ? (void)(f = stream_kernel_vph<T, U, D, R, S, G, 0>(vph, vs)) : (void)0), ...);
-    return f;
-}
-template <typename T>
-static StreamKernel stream_kernel(const FlreluPlan& pl, int i) {
-    typedef std::integer_sequence<int, 0, 1> V2;
-    typedef std::integer_sequence<int, 0, 1, 2, 3> V4;
-    typedef std::integer_sequence<int, 0, 1, 2, 5, 6> Forward;     // separable | 12x12 | 12x12 flipped | 12x12 with mirror-symmetric rows | the same, flipped
-    typedef std::integer_sequence<int, 0, 3, 4> Adjoint;           // separable | 12x12 up filter | the same, flipped
-    const int U = pl.U[i], D = pl.D[i], V = pl.VPH[i], R = pl.RADIAL[i], S = pl.SIGNS[i], G = pl.G[i];
-    if (pl.WIDE[i]) {                                              // the earlier form of the up-4 separable plain forward
-        if (U != 4 || D != 2 || R != 0 || S != 0) return nullptr;
-        return G == 1 ? stream_kernel_vph<T, 4, 2, 0, 0, 1, 1>(V, V2()) : G == 2 ? stream_kernel_vph<T, 4, 2, 0, 0, 2, 1>(V, V2()) : nullptr;
-    }
-    if (S == 2) {                                                  // adjoint: up 2, one plane per wave
-        if (U != 2 || G != 1) return nullptr;
-        return D == 2 ? stream_kernel_radial<T, 2, 2, 2, 1>(R, V, V2(), Adjoint()) : D == 4 ? stream_kernel_radial<T, 2, 4, 2, 1>(R, V, V4(), Adjoint()) : nullptr;
-    }
-    if (D != 2 || (U != 2 && U != 4)) return nullptr;
-    if (S == 1 && G == 1) return U == 2 ? stream_kernel_radial<T, 2, 2, 1, 1>(R, V, V2(), Forward()) : stream_kernel_radial<T, 4, 2, 1, 1>(R, V, V2(), Forward());
-    if (S == 0 && G == 1) return U == 2 ? stream_kernel_radial<T, 2, 2, 0, 1>(R, V, V2(), Forward()) : stream_kernel_radial<T, 4, 2, 0, 1>(R, V, V2(), Forward());
-    if (S == 0 && G == 2) return U == 2 ? stream_kernel_radial<T, 2, 2, 0, 2>(R, V, V2(), Forward()) : stream_kernel_radial<T, 4, 2, 0, 2>(R, V, V2(), Forward());
-    return nullptr;
+// a trip starts at any of the D down phases
+template <typename T, int U, int D, int R, int S, int G, int W>
+StreamKernel stream_kernel_leaf(int vph) {
+    return stream_kernel_vph<T, U, D, R, S, G, W>(vph, std::make_integer_sequence<int, D>());
 }
 
-template <typename T>
-static int launch_stream(const sg3_filtered_lrelu_params& q, const FlreluPlan& pl, hipStream_t st) {
-    StreamParams p;
-    p.x = q.x; p.y = q.y; p.b = q.b; p.fu = q.fu; p.fd = q.fd;
-    p.C = q.C; p.planes = q.N * q.C; p.xH = q.xH; p.xW = q.xW; p.yH = q.yH; p.yW = q.yW;
-    p.xsN = q.xStride[0]; p.xsC = q.xStride[1]; p.xsH = q.xStride[2];
-    p.ysN = q.yStride[0]; p.ysC = q.yStride[1]; p.ysH = q.yStride[2];
-    p.bStride = q.bStride;
-    p.px0 = q.px0; p.py0 = q.py0;
-    p.gain = q.gain; p.slope = q.slope; p.clamp = q.clamp; p.flip = q.flip;
-    p.fastAct = pl.fastAct;
-
-    p.s = q.s; p.sH = q.sH; p.sWb = q.sWbytes; p.sx = q.sx; p.sy = q.sy;
-    p.ysum = q.ySumPartial;
-    p.ymax = q.yAbsMaxPartial;
-#ifdef SG3_STAMPS
-    p.stamps = g_stamps;
+// ---------------------------------------------------------------------------
+// The part table: every leaf <T, U, D, R, S, G, W> the host's lookup can ask for (38 per tensor type, 82 kernels), each in exactly
+// one part.  Part = 6 * (tensor type: float 0, half 1) + family:
+//   0  plain forward, separable filters (both up factors, one and two planes per wave, the WIDE forms): the 24 kernels whose
+//      assembly tests/test_flrelu_isa_budget_cpu.py and tests/test_flrelu_up4_resources_cpu.py read (parts 0 and 6)
+//   1  plain forward, 12x12 down filter (RADIAL 1)
+//   2  the same, flipped (RADIAL 2)
+//   3  plain forward, 12x12 down filter with mirror-symmetric rows (RADIAL 5 | 6)
+//   4  the adjoints, and the sign-writing forward with separable filters
+//   5  the sign-writing forward with a 12x12 down filter
+// cut by measured compile time: no part takes as long as sg3_modconv.hip; the whole file in one piece takes minutes.
+//
+// A kernel compiles to the same instructions in its part as in the whole file only while the part keeps the VARIETY of constants
+// the whole file passes to the helpers that are not force-inlined -- floor_div / ceil_div_s (sg3_common.h) with b = U, and
+// fast_threshold with (taps, up) = (6 U, U) from the plain forward.  They have internal linkage, so when every call in the
+// translation unit passes the same constant, interprocedural constant propagation puts it into the helper's body before the
+// inliner runs, and the prologue arithmetic comes out in another shape (the scalar registers behind it shift by one or two, a scalar
+// spill appears or goes: 164 of 164 kernels differed when each leaf was compiled alone, none does with these parts).  Hence every
+// part holds up-2 AND up-4 leaves, and a part that holds plain-forward leaves holds them of both up factors.
+#ifndef SG3_FLRELU_PART
+#define SG3_FLRELU_PART -1                       // every part: the tools and the dispatch recorder include this file as it stands
 #endif
-    p.nChunks = pl.nChunks; p.CH = pl.chunkRows;
-    for (int i = 0; i < pl.launches; i++) {
-        p.nStrips = pl.nStrips[i]; p.TW = pl.TW[i]; p.ox0Base = pl.ox0Base[i]; p.wideBlocks = pl.wideBlocks[i]; p.totalBlocks = pl.totalBlocks[i];
-        const StreamKernel kernel = stream_kernel<T>(pl, i);
-        if (!kernel) {
-            set_error("filtered_lrelu: no flrelu_stream_kernel<U=%d, D=%d, VPH=%d, RADIAL=%d, SIGNS=%d, G=%d, WIDE=%d>", pl.U[i], pl.D[i], pl.VPH[i],
-                      pl.RADIAL[i], pl.SIGNS[i], pl.G[i], pl.WIDE[i]);
-            return SG3_NO_KERNEL;
-        }
-        hipLaunchKernelGGL(kernel, dim3((unsigned)p.totalBlocks), dim3(64), 0, st, p);
-        SG3_LAUNCH_CHECK("flrelu_stream_kernel");
-    }
-    return SG3_OK;
-}
-
-template <typename T>
-static int launch_pointwise(const sg3_filtered_lrelu_params& q, const FlreluPlan& pl, hipStream_t st) {
-    PointParams p;
-    p.x = q.x; p.y = q.y; p.b = q.b; p.fu = q.fu; p.fd = q.fd;
-    p.N = q.N; p.C = q.C; p.H = q.xH; p.W = q.xW; p.yH = q.yH; p.yW = q.yW;
-    for (int i = 0; i < 4; i++) { p.xs[i] = q.xStride[i]; p.ys[i] = q.yStride[i]; }
-    p.bStride = q.bStride; p.px0 = q.px0; p.py0 = q.py0;
-    p.gain = q.gain; p.slope = q.slope; p.clamp = q.clamp;
-    hipLaunchKernelGGL((flrelu_pointwise_kernel<T>), dim3((unsigned)pl.totalBlocks[0]), dim3(256), 0, st, p);
-    SG3_LAUNCH_CHECK("flrelu_pointwise_kernel");
-    return SG3_OK;
-}
+#define SG3_FLRELU_HERE(k) (SG3_FLRELU_PART < 0 || SG3_FLRELU_PART == (k))
+#define LEAF(T, U, D, R, S, G, W) template StreamKernel stream_kernel_leaf<T, U, D, R, S, G, W>(int);
+#define LEAVES_PLAIN_SEPARABLE(T) \
+    LEAF(T, 4, 2, 0, 0, 1, 1) LEAF(T, 4, 2, 0, 0, 2, 1) LEAF(T, 2, 2, 0, 0, 1, 0) LEAF(T, 4, 2, 0, 0, 1, 0) LEAF(T, 2, 2, 0, 0, 2, 0) LEAF(T, 4, 2, 0, 0, 2, 0)
+#define LEAVES_PLAIN_RADIAL(T, R) LEAF(T, 2, 2, R, 0, 1, 0) LEAF(T, 4, 2, R, 0, 1, 0) LEAF(T, 2, 2, R, 0, 2, 0) LEAF(T, 4, 2, R, 0, 2, 0)
+#define LEAVES_ADJOINT_AND_SEPARABLE_SIGNS(T) \
+    LEAF(T, 2, 2, 0, 2, 1, 0) LEAF(T, 2, 2, 3, 2, 1, 0) LEAF(T, 2, 2, 4, 2, 1, 0) LEAF(T, 2, 4, 0, 2, 1, 0) LEAF(T, 2, 4, 3, 2, 1, 0) LEAF(T, 2, 4, 4, 2, 1, 0) \
+    LEAF(T, 2, 2, 0, 1, 1, 0) LEAF(T, 4, 2, 0, 1, 1, 0)
+#define LEAVES_RADIAL_SIGNS(T) \
+    LEAF(T, 2, 2, 1, 1, 1, 0) LEAF(T, 2, 2, 2, 1, 1, 0) LEAF(T, 2, 2, 5, 1, 1, 0) LEAF(T, 2, 2, 6, 1, 1, 0) \
+    LEAF(T, 4, 2, 1, 1, 1, 0) LEAF(T, 4, 2, 2, 1, 1, 0) LEAF(T, 4, 2, 5, 1, 1, 0) LEAF(T, 4, 2, 6, 1, 1, 0)
+#if SG3_FLRELU_HERE(0)
+LEAVES_PLAIN_SEPARABLE(float)
+#endif
+#if SG3_FLRELU_HERE(1)
+LEAVES_PLAIN_RADIAL(float, 1)
+#endif
+#if SG3_FLRELU_HERE(2)
+LEAVES_PLAIN_RADIAL(float, 2)
+#endif
+#if SG3_FLRELU_HERE(3)
+LEAVES_PLAIN_RADIAL(float, 5) LEAVES_PLAIN_RADIAL(float, 6)
+#endif
+#if SG3_FLRELU_HERE(4)
+LEAVES_ADJOINT_AND_SEPARABLE_SIGNS(float)
+#endif
+#if SG3_FLRELU_HERE(5)
+LEAVES_RADIAL_SIGNS(float)
+#endif
+#if SG3_FLRELU_HERE(6)
+LEAVES_PLAIN_SEPARABLE(_Float16)
+#endif
+#if SG3_FLRELU_HERE(7)
+LEAVES_PLAIN_RADIAL(_Float16, 1)
+#endif
+#if SG3_FLRELU_HERE(8)
+LEAVES_PLAIN_RADIAL(_Float16, 2)
+#endif
+#if SG3_FLRELU_HERE(9)
+LEAVES_PLAIN_RADIAL(_Float16, 5) LEAVES_PLAIN_RADIAL(_Float16, 6)
+#endif
+#if SG3_FLRELU_HERE(10)
+LEAVES_ADJOINT_AND_SEPARABLE_SIGNS(_Float16)
+#endif
+#if SG3_FLRELU_HERE(11)
+LEAVES_RADIAL_SIGNS(_Float16)
+#endif
+#if SG3_FLRELU_PART > 11
+#error "sg3_filtered_lrelu.hip has parts 0 .. 11 (csrc/Makefile: FLRELU_PARTS)"
+#endif
+#undef LEAVES_RADIAL_SIGNS
+#undef LEAVES_ADJOINT_AND_SEPARABLE_SIGNS
+#undef LEAVES_PLAIN_RADIAL
+#undef LEAVES_PLAIN_SEPARABLE
+#undef LEAF
 
 } // namespace sg3
-
-extern "C" {
-
-int sg3_filtered_lrelu_has_kernel(int up, int down, int fuW, int fuH, int fdW, int fdH) {
-    return (sg3::stream_supported(up, down, fuW, fuH, fdW, fdH) || sg3::pointwise_supported(up, down, fuW, fuH, fdW, fdH)) ? 1 : 0;
-}
-
-int sg3_filtered_lrelu_sum_slots(int N, int C, int yH, int yW, int down) {
-    if (N <= 0 || C <= 0 || yH <= 0 || yW <= 0 || (down != 2 && down != 4)) return 0;
-    int nStrips, TW, nChunks, CH;
-    sg3::stream_grid(N, C, yH, yW, down, nStrips, TW, nChunks, CH);
-    return nStrips * nChunks;
-}
-
-int sg3_filtered_lrelu_finish_partials(const float* sumPartial, const float* absMaxPartial, int N, int C, int slots, float* db, float* absMax, void* stream) {
-    using namespace sg3;
-    SG3_REQUIRE(sumPartial && db && N > 0 && C > 0 && slots > 0, "filtered_lrelu_finish_partials: bad arguments");
-    SG3_REQUIRE(!absMax == !absMaxPartial, "filtered_lrelu_finish_partials: absMaxPartial and absMax come together");
-    hipLaunchKernelGGL(flrelu_finish_partials_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, sumPartial, absMaxPartial, N, C, slots, db, absMax);
-    SG3_LAUNCH_CHECK("flrelu_finish_partials_kernel");
-    return SG3_OK;
-}
-
-int sg3_filtered_lrelu_shape(int xH, int xW, int up, int down, int fuW, int fuH, int fdW, int fdH,
-                             int px0, int px1, int py0, int py1, int* yH, int* yW, int* sH, int* sWbytes, int* swLimit) {
-    using namespace sg3;
-    SG3_REQUIRE(xH > 0 && xW > 0, "x is empty");
-    SG3_REQUIRE(up >= 1 && down >= 1, "up and down must be at least 1");
-    SG3_REQUIRE(fuW >= 1 && fdW >= 1, "fu and fd must not be empty");
-    // separable filters have the same extent along both axes (reference :63-66 uses size(0) for the height)
-    const int64_t fut_w = fuW - 1, fut_h = (fuH ? fuH : fuW) - 1;
-    const int64_t fdt_w = fdW - 1, fdt_h = (fdH ? fdH : fdW) - 1;
-    const int64_t cw = (int64_t)xW * up + (px0 + px1) - fut_w;
-    const int64_t ch = (int64_t)xH * up + (py0 + py1) - fut_h;
-    SG3_REQUIRE(cw > fdt_w && ch > fdt_h, "upsampled buffer must be at least the size of downsampling filter");
-    SG3_REQUIRE(cw <= INT32_MAX && ch <= INT32_MAX, "upsampled buffer is too large");
-    const int64_t ow = (cw - fdt_w + (down - 1)) / down;
-    const int64_t oh = (ch - fdt_h + (down - 1)) / down;
-    SG3_REQUIRE(ow > 0 && oh > 0, "output must be at least 1x1");
-    const int64_t sw_active = ow * down - (down - 1) + fdt_w;
-    const int64_t sh = oh * down - (down - 1) + fdt_h;
-    const int64_t sw = (sw_active + 15) & ~(int64_t)15;
-    SG3_REQUIRE(sh <= INT32_MAX && (sw >> 2) <= INT32_MAX, "signs is too large");
-    if (yH) *yH = (int)oh;
-    if (yW) *yW = (int)ow;
-    if (sH) *sH = (int)sh;
-    if (sWbytes) *sWbytes = (int)(sw >> 2);
-    if (swLimit) *swLimit = (int)((sw_active + 3) >> 2);
-    return SG3_OK;
-}
-
-float sg3_filtered_lrelu_fast_threshold(const float* fu, int fuW, int up, float gain, float slope, float clamp) {
-    if (!fu || up < 1 || fuW < up) return -1.f;
-    return sg3::fast_threshold(fu, fuW, up, gain, slope, clamp);
-}
-
-int sg3_filtered_lrelu_force_up4_wide(int wide) { return sg3::g_up4_wide.exchange(wide ? 1 : 0); }
-
-// the plan of a call the older queries answer for: a tensor type the kernels have and a non-empty output, nothing else checked
-static bool query_plan(const sg3_filtered_lrelu_params* p, sg3::FlreluPlan& pl) {
-    if (!p || (p->dtype != SG3_F32 && p->dtype != SG3_F16) || p->N <= 0 || p->C <= 0 || p->yH <= 0 || p->yW <= 0) return false;
-    pl = sg3::plan_filtered_lrelu(*p, sg3::FlreluKnobs::env(), sg3::g_up4_wide.load(std::memory_order_relaxed));
-    return pl.kind == SG3_FLRELU_STREAM;
-}
-
-int sg3_filtered_lrelu_planes_per_wave(const sg3_filtered_lrelu_params* p) {
-    sg3::FlreluPlan pl;
-    return query_plan(p, pl) ? pl.planesPerWave : 0;
-}
-
-int sg3_filtered_lrelu_stream_grid(const sg3_filtered_lrelu_params* p, int* nStrips, int* stripW, int* nFullStrips, int* nChunks, int* chunkRows) {
-    sg3::FlreluPlan pl;
-    if (!query_plan(p, pl)) return 0;                                   // not a streaming-kernel call
-    const bool mixed = pl.planesPerWave == 3;                           // launch 0 takes the full strips, one more strip follows them
-    if (nStrips) *nStrips = pl.nStrips[0] + (mixed ? 1 : 0);
-    if (stripW) *stripW = pl.TW[0];
-    if (nFullStrips) *nFullStrips = mixed ? pl.nStrips[0] : 0;
-    if (nChunks) *nChunks = pl.nChunks;
-    if (chunkRows) *chunkRows = pl.chunkRows;
-    return 1;
-}
-
-int sg3_filtered_lrelu_dispatch(const sg3_filtered_lrelu_params* p, sg3_filtered_lrelu_dispatch_info* out) {
-    using namespace sg3;
-    SG3_REQUIRE(p && out, "filtered_lrelu_dispatch: null argument");
-    SG3_REQUIRE(p->N > 0 && p->C > 0 && p->xH > 0 && p->xW > 0, "filtered_lrelu: x is empty");
-    SG3_REQUIRE(p->yH > 0 && p->yW > 0, "filtered_lrelu: output must be at least 1x1");
-    SG3_REQUIRE(p->up >= 1 && p->down >= 1, "filtered_lrelu: up and down must be at least 1");
-    SG3_REQUIRE(p->dtype == SG3_F32 || p->dtype == SG3_F16, "filtered_lrelu: x must be float16 or float32");
-    SG3_REQUIRE(!(p->writeSigns && p->readSigns), "filtered_lrelu: cannot read and write signs in one call");
-    *out = plan_filtered_lrelu(*p, FlreluKnobs::env(), g_up4_wide.load(std::memory_order_relaxed));
-    if (out->kind == SG3_FLRELU_NONE) {
-        set_error("filtered_lrelu: no fused kernel for up=%d down=%d fu=%dx%d fd=%dx%d signs=%d", p->up, p->down,
-                  p->fuW, p->fuH, p->fdW, p->fdH, (int)(p->writeSigns || p->readSigns));
-        return SG3_NO_KERNEL;
-    }
-    SG3_REQUIRE(out->launches > 0, "filtered_lrelu: grid too large");
-    return SG3_OK;
-}
-
-int sg3_filtered_lrelu(const sg3_filtered_lrelu_params* p, void* stream) {
-    using namespace sg3;
-    SG3_REQUIRE(p && p->x && p->y && p->fu && p->fd, "filtered_lrelu: null tensor");
-    FlreluPlan pl;
-    const int rc = sg3_filtered_lrelu_dispatch(p, &pl);
-    if (rc != SG3_OK) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (pl.kind == SG3_FLRELU_POINTWISE) return p->dtype == SG3_F32 ? launch_pointwise<float>(*p, pl, st) : launch_pointwise<_Float16>(*p, pl, st);
-    return p->dtype == SG3_F32 ? launch_stream<float>(*p, pl, st) : launch_stream<_Float16>(*p, pl, st);
-}
-
-} // extern "C"

@@ -16,8 +16,9 @@ template <int KS> struct ConvK { static_assert(KS == 1 || KS == 3, "kernel size 
 
 // Hardware block id -> logical block id of a 1-D grid of nb blocks: the hardware deals consecutive ids round-robin to the 8 XCDs;
 // renumbered, every XCD gets one run of consecutive logical ids (blocks that share operands share its L2).
-// flrelu_stream_kernel (sg3_filtered_lrelu.hip) spells the same two lines out on purpose: profiles/flrelu_traffic*.json carry that
-// file's hash (tests/test_tools_cpu.py), so an edit there means re-collecting them.
+// flrelu_stream_kernel (sg3_filtered_lrelu.hip, the kernel file of filtered_lrelu: its host side is sg3_flrelu_host.hip) spells the
+// same two lines out on purpose: profiles/flrelu_traffic*.json carry the kernel file's hash (tests/test_tools_cpu.py), so an edit
+// there means re-collecting them.
 __device__ __forceinline__ int xcd_block(int bid, int nb) {
     const int q = nb >> 3, r = nb & 7, xcd = bid & 7, k = bid >> 3;
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;

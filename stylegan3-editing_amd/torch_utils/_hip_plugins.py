@@ -167,6 +167,13 @@ class FilteredLreluPlugin:
         with torch.cuda.device(x.device):
             rc = lib.sg3_filtered_lrelu(ctypes.byref(p), abi.stream_ptr(x.device))
         if abi.check(rc, 'sg3_filtered_lrelu', allow_no_kernel=True) == abi.SG3_NO_KERNEL:
+            # "this call has no fused kernel" (the plan names none: the caller composes the generic ops) is not "the kernel the plan
+            # names is missing from the library" -- that one is a broken build, and the generic composition would only hide it
+            error = abi.last_error()
+            info = abi.FilteredLreluDispatchInfo()
+            lib.sg3_filtered_lrelu_dispatch(ctypes.byref(p), ctypes.byref(info))
+            if info.kind != abi.SG3_FLRELU_NONE:
+                raise RuntimeError(f'sg3_filtered_lrelu failed (rc={rc}): {error}')
             return _no_kernel(return_sum, return_amax)
         if return_sum:
             ysum = amax = None

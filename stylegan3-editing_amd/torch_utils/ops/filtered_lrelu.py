@@ -33,7 +33,7 @@ def _init():
     global _plugin
     if _plugin is None:
         _plugin = custom_ops.get_plugin(module_name='filtered_lrelu_plugin',
-                                        sources=['sg3_filtered_lrelu.hip', 'sg3_bias_act.hip'],
+                                        sources=['sg3_filtered_lrelu.hip', 'sg3_flrelu_host.hip', 'sg3_bias_act.hip'],
                                         source_dir=os.path.join(os.path.dirname(__file__), '..', '..', 'csrc'))
     return True
 

@@ -1,14 +1,16 @@
 """Regenerates tests/golden/flrelu_dispatch.json: what sg3_filtered_lrelu launches for a fixed list of calls.
 
-The table is RECORDED, not computed by the code it pins: csrc/sg3_filtered_lrelu.hip is compiled with modconv_dispatch_recorder.h
-force-included (the launch macro writes down kernel name with template arguments, grid, workgroup and the work decomposition of the
-parameter block) and linked with flrelu_dispatch_recorder.cpp; this script makes the list of calls, runs that program and stores the
-result.  The committed table came from the commit BEFORE the choice moved into csrc/sg3_flrelu_plan.h.
+The table is RECORDED, not computed by the code it pins: the host side, csrc/sg3_flrelu_host.hip, is compiled with
+modconv_dispatch_recorder.h force-included (the launch macro writes down kernel name with template arguments, grid, workgroup and the
+work decomposition of the parameter block) and linked with the kernel file (csrc/sg3_filtered_lrelu.hip in one piece, every part: its
+host stubs are what the recorder names) and flrelu_dispatch_recorder.cpp; this script makes the list of calls, runs that program and
+stores the result.  The committed table came from the commit BEFORE the choice moved into csrc/sg3_flrelu_plan.h.
 
     hipcc -O1 -std=c++17 -fPIC --offload-arch=gfx950 -fno-honor-nans -Iinclude -I<csrc> -include tests/golden/modconv_dispatch_recorder.h \
-          -c <csrc>/sg3_filtered_lrelu.hip -o a.o
+          -c <csrc>/sg3_flrelu_host.hip -o a.o
+    hipcc -O1 -std=c++17 -fPIC --offload-arch=gfx950 -fno-honor-nans -Iinclude -I<csrc> -c <csrc>/sg3_filtered_lrelu.hip -o k.o
     hipcc -O1 -std=c++17 --offload-arch=gfx950 -x hip -c tests/golden/flrelu_dispatch_recorder.cpp -o m.o
-    hipcc -rdynamic m.o a.o -ldl -o recorder
+    hipcc -rdynamic m.o a.o k.o -ldl -o recorder
     python tests/golden/make_flrelu_dispatch.py recorder            # needs the built library for sg3_filtered_lrelu_shape
 """
 import ctypes

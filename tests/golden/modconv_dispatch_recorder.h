@@ -1,8 +1,9 @@
 // modconv_dispatch_recorder.h -- force-included (-include) in front of csrc/sg3_modconv.hip and csrc/sg3_modconv_f23.hip to
 // record what their host side WOULD launch, without a GPU: the launch macro, the dynamic-LDS attribute call and the device
 // queries are replaced after <hip/hip_runtime.h> has declared the real ones.  Used once per change of the dispatch to regenerate
-// tests/golden/modconv_dispatch.json (see make_modconv_dispatch.py); never part of the product library.  csrc/sg3_filtered_lrelu.hip
-// is recorded the same way for tests/golden/flrelu_dispatch.json (make_flrelu_dispatch.py, flrelu_dispatch_recorder.cpp), and
+// tests/golden/modconv_dispatch.json (see make_modconv_dispatch.py); never part of the product library.  csrc/sg3_flrelu_host.hip
+// (the host side of filtered_lrelu; the kernel file, csrc/sg3_filtered_lrelu.hip, is linked to it as it stands) is recorded the same
+// way for tests/golden/flrelu_dispatch.json (make_flrelu_dispatch.py, flrelu_dispatch_recorder.cpp), and
 // csrc/sg3_conv2d.hip, sg3_conv2d_dgrad.hip and sg3_conv2d_wgrad_sum.hip for tests/golden/conv2d_dispatch.json
 // (make_conv2d_dispatch.py, conv2d_dispatch_recorder.cpp).
 #pragma once

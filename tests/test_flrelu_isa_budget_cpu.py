@@ -13,8 +13,9 @@ import tempfile
 
 import pytest
 
+import flrelu_parts
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'stylegan3-editing_amd', 'csrc')
 
 # <T, U, D, VPH, RADIAL, SIGNS, G, WIDE>: (.vgpr_count, fast-loop VALU per six-row trip) of the parent commit
 PARENT = {
@@ -43,17 +44,12 @@ FIR_CHAINS = {2: 6 * (12 + 24 + 24 + 12), 4: 6 * (12 + 48 + 48 + 24)}
 
 @pytest.fixture(scope='module')
 def counts():
-    """tools/count_flrelu_isa.py --json over the assembly of csrc/sg3_filtered_lrelu.hip; the flags are csrc/Makefile's"""
+    """tools/count_flrelu_isa.py --json over the assembly of the parts of csrc/sg3_filtered_lrelu.hip that hold the separable plain
+    forward (its part table: family 0 of either tensor type), compiled side by side; the flags are csrc/Makefile's"""
     tmp = tempfile.mkdtemp(prefix='sg3_flrelu_isa_')
     try:
-        subprocess.check_call(['/opt/rocm/bin/hipcc', '-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-fvisibility=hidden', '-fno-honor-nans',
-                               '--cuda-device-only', '-I' + CSRC, '-I' + os.path.join(ROOT, 'include'), '-c',
-                               os.path.join(CSRC, 'sg3_filtered_lrelu.hip'), '-save-temps', '-o', os.path.join(tmp, 'flrelu.o')],
-                              cwd=tmp, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        asm = [f for f in os.listdir(tmp) if f.endswith('gfx950.s')]
-        assert len(asm) == 1, asm
-        out = subprocess.run([sys.executable, os.path.join(ROOT, 'tools', 'count_flrelu_isa.py'), os.path.join(tmp, asm[0]), '--json'],
-                             capture_output=True, text=True)
+        asm = flrelu_parts.assembly(tmp, flrelu_parts.PLAIN_SEPARABLE)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, 'tools', 'count_flrelu_isa.py'), *asm, '--json'], capture_output=True, text=True)
         assert out.returncode == 0, out.stderr
     finally:
         shutil.rmtree(tmp, ignore_errors=True)

@@ -3,33 +3,28 @@
 A SIMD lane has 512 vector registers, so a kernel is resident at four waves per SIMD when it needs at most 512 / 4 = 128 of them
 (architectural + accumulator).  The up-4 separable plain forward must stay there without scratch, without spilled vector registers
 and without spilled scalars moving through v_readlane / v_writelane inside its row loops; the up-2 forms must not grow past it."""
-import os
 import re
 import shutil
-import subprocess
 import tempfile
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'stylegan3-editing_amd', 'csrc')
+import flrelu_parts
+
 WAVES = 4
 VGPR_BUDGET = 512 // WAVES
 
 
 @pytest.fixture(scope='module')
 def listing():
-    """{demangled template arguments: (metadata, body lines)} of every flrelu_stream_kernel; the flags are csrc/Makefile's."""
+    """{demangled template arguments: (metadata, body lines)} of every separable plain-forward flrelu_stream_kernel (the parts of
+    csrc/sg3_filtered_lrelu.hip that hold them, compiled side by side); the flags are csrc/Makefile's."""
     tmp = tempfile.mkdtemp(prefix='sg3_flrelu_res_')
     try:
-        subprocess.check_call(['/opt/rocm/bin/hipcc', '-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-fvisibility=hidden', '-fno-honor-nans',
-                               '--cuda-device-only', '-I' + CSRC, '-I' + os.path.join(ROOT, 'include'), '-c',
-                               os.path.join(CSRC, 'sg3_filtered_lrelu.hip'), '-save-temps', '-o', os.path.join(tmp, 'flrelu.o')],
-                              cwd=tmp, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        asm = [f for f in os.listdir(tmp) if f.endswith('gfx950.s')]
-        assert len(asm) == 1, asm
-        with open(os.path.join(tmp, asm[0])) as f:
-            text = f.read()
+        text = ''
+        for path in flrelu_parts.assembly(tmp, flrelu_parts.PLAIN_SEPARABLE):
+            with open(path) as f:
+                text += f.read()
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
     lines = text.split('\n')

@@ -1,8 +1,12 @@
 """Instruction budget of the streaming filtered_lrelu plain forward, counted in the compiler's gfx950 assembly.
 
-    hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -fvisibility=hidden -fno-honor-nans --cuda-device-only \\
+    hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -fvisibility=hidden -fno-honor-nans --cuda-device-only -DSG3_FLRELU_PART=0 \\
           -Istylegan3-editing_amd/csrc -Iinclude -c stylegan3-editing_amd/csrc/sg3_filtered_lrelu.hip -save-temps -o /tmp/flrelu.o
-    python tools/count_flrelu_isa.py sg3_filtered_lrelu-hip-amdgcn-amd-amdhsa-gfx950.s [--json] [--all]
+    python tools/count_flrelu_isa.py sg3_filtered_lrelu-hip-amdgcn-amd-amdhsa-gfx950.s [more.s ...] [--json] [--all]
+
+The kernel file is compiled in parts (its part table; the library links all twelve): -DSG3_FLRELU_PART=0 and =6 hold the separable
+plain forward for float and half, without the macro the one compile holds every kernel (minutes, and the same instructions).  Several
+assembly files -- one per part, each compiled in a directory of its own -- are read as one.
 
 For every separable plain-forward instantiation flrelu_stream_kernel<T, U, 2, VPH, 0, 0, G, WIDE> (--all: every instantiation) it
 prints the vector instructions of one six-row trip of the fast loop (one-instruction activation: v_med3 alone) and of the redo loop
@@ -95,12 +99,15 @@ def analyse(text, every=False):
 
 def main():
     argv = [a for a in sys.argv[1:] if not a.startswith('--')]
-    if len(argv) != 1:
+    if not argv:
         sys.exit(__doc__)
-    with open(argv[0]) as f:
-        res = analyse(f.read(), every='--all' in sys.argv)
+    text = ''
+    for path in argv:                                      # one assembly file per part: kernel names are unique across them
+        with open(path) as f:
+            text += f.read()
+    res = analyse(text, every='--all' in sys.argv)
     if not res:
-        sys.exit('no flrelu_stream_kernel in ' + argv[0])
+        sys.exit('no flrelu_stream_kernel in ' + ' '.join(argv))
     if '--json' in sys.argv:
         print(json.dumps(res, indent=1))
         return

@@ -10,7 +10,8 @@
 // L11 1208 / 1209 / 1216 us; it does to the convolution that writes those rows).
 // Build + run on the GPU box:
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-honor-nans -DSG3_STAMPS tools/flrelu_clock.hip -o /tmp/fc && /tmp/fc
-#include "../stylegan3-editing_amd/csrc/sg3_filtered_lrelu.hip"
+#include "../stylegan3-editing_amd/csrc/sg3_filtered_lrelu.hip"      // the kernels: every part in this one compile (minutes)
+#include "../stylegan3-editing_amd/csrc/sg3_flrelu_host.hip"          // launchers and entry points
 #include <algorithm>
 #include <cstdlib>
 #include <vector>

@@ -12,7 +12,8 @@
 // filtered_lrelu itself <= ~0.68 ms.  If build 2 is not clearly below that, no fused kernel can be.
 // Build + run on the GPU box (three binaries):
 //   for b in 0 1 2; do hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-honor-nans $([ $b -gt 0 ] && echo -DSG3_FUSION_BOUND=$b) tools/flrelu_fusion_bound.hip -o /tmp/fb$b && /tmp/fb$b; done
-#include "../stylegan3-editing_amd/csrc/sg3_filtered_lrelu.hip"
+#include "../stylegan3-editing_amd/csrc/sg3_filtered_lrelu.hip"      // the kernels: every part in this one compile (minutes)
+#include "../stylegan3-editing_amd/csrc/sg3_flrelu_host.hip"          // launchers and entry points
 #include <vector>
 
 namespace sg3 { void set_error(const char* fmt, ...) { va_list a; va_start(a, fmt); vfprintf(stderr, fmt, a); va_end(a); fputc('\n', stderr); } }
